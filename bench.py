@@ -21,6 +21,9 @@ Printed JSON (one line, rank 0):
   cpu_baseline  the CPU oracle (oracle/, "port": the reference has no CPU path) timed on
               this host's cores on a row sample of the same matrix, N = 1 only.
 
+--dump-outputs DIR writes what the last timed step computed -- the factors X (x.npy) and Theta (theta.npy) -- after the
+timed region (dump_outputs); the inputs depend on --seed only, so two builds can be compared output for output.
+
 N > 1 on a box with fewer GPUs than ranks (tests): CUMF_BENCH_BACKEND=gloo stands in for RCCL (collectives
 staged through the host) and ranks share devices (local_rank % device_count).
 """
@@ -49,6 +52,24 @@ def alg_bytes(nnz: int, rows: int, f: int, cg: bool) -> float:
     if cg:
         b += 4.0 * f * rows
     return b
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: write each device array as out_dir/<name>.npy (float32).  When they exceed DUMP_BYTES together,
+    every array keeps the same fraction of its rows: a sorted sample drawn by np.random.RandomState(0), so the rows
+    depend only on the shapes and two builds of the project are compared row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    keep = min(1.0, (DUMP_BYTES - 4096 * len(arrays)) / max(total, 1))
+    for name, t in arrays.items():
+        rows = t.shape[0]
+        if keep < 1.0:
+            idx = np.sort(np.random.RandomState(0).choice(rows, int(rows * keep), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def cpu_baseline(d, f, lam, solver, target_s=16.0):
@@ -689,7 +710,12 @@ def main() -> int:
     ap.add_argument("--no-rmse-log", action="store_true",
                     help="skip the 10-iteration doALS-vs-oracle RMSE log of the parity_at_scale leg (~2 min of oracle)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the factors of the last timed step as DIR/x.npy and DIR/theta.npy "
+                         "(float32; rank 0's; a fixed row sample when they exceed 64 MB: see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a.gpus)
 
@@ -834,6 +860,8 @@ def main() -> int:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"x": eng.XT, "theta": eng.thetaT})
 
     diag = None
     if world > 1:

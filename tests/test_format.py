@@ -15,6 +15,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_hostutil.so")
+# what the reference's loaders read from the dataset below, stored by tests/golden/make_format_golden.py
+REF_GOLDEN = os.path.join(ROOT, "tests", "golden", "fmt_ref_loaders.npz")
+DATASET, DATASET_SEED = (37, 23, 300, 60), 9
 
 MANGLED = {
     "csr": "_Z22loadCSRSparseMatrixBinPKcS0_S0_PfPiS2_il",
@@ -59,7 +62,7 @@ def _load_with(lib, d, m, n, nnz, nnz_test):
 def dataset(tmp_path_factory):
     from cumf_als_amd import datagen
 
-    r = datagen.synth_ratings(37, 23, 300, 60, seed=9)
+    r = datagen.synth_ratings(*DATASET, seed=DATASET_SEED)
     d = str(tmp_path_factory.mktemp("fmt"))
     datagen.write_dataset(r, d)
     return r, d
@@ -95,10 +98,20 @@ def test_structure_matches_scipy(dataset):
     assert (np.diff(d["csr_indptr"]) > 0).all() and (np.diff(d["csc_indptr"]) > 0).all()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (reference not mounted at build time)")
 def test_reference_loaders_read_our_files(dataset):
+    """The reference's loaders are plain freads of headerless 4-byte elements, so files holding the bytes they read
+    (tests/golden/fmt_ref_loaders.npz) load identically; the loaders themselves run too where oracle/_ref is built."""
+    from cumf_als_amd import datagen
+
     r, d = dataset
-    ref = _load_with(C.CDLL(REF_SO), d, r.m, r.n, r.nnz, r.nnz_test)
+    z = np.load(REF_GOLDEN)
+    ref = {k: z[k] for k in z.files}
+    for key, (name, dtype) in datagen.FILES.items():
+        assert ref[key].dtype == dtype and np.fromfile(os.path.join(d, name), dtype).tobytes() == ref[key].tobytes(), key
+    if os.path.exists(REF_SO):
+        live = _load_with(C.CDLL(REF_SO), d, r.m, r.n, r.nnz, r.nnz_test)
+        for k, v in ref.items():
+            assert np.array_equal(live[k], v), k
     for k, v in r.numpy().items():
         assert np.array_equal(ref[k], v), k
 
