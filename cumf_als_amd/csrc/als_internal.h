@@ -81,19 +81,20 @@ struct KernelArgs {
   // dense_slots: item i (wave kernel) / row i (reduce kernel) of this launch uses slot i of `part` and
   // every item is dumped, none solved in place (batched "Gram -> tiles -> solver kernel" path)
   int dense_slots;
-  int whole_only;  // no item of the launch has a slot (the plan has no chunked rows): the LU wave kernel without its dump exit
+  int whole_only;  // host-only, no longer read (the route decides; the field keeps the kernels' argument layout)
   long long row_begin;
   int f;
   float lambda;
   int cg_iters;
   int dbg;  // ablation switches; read only by the kernels of the profiling build (-DCUMF_ABLATE=1, libALS_ablate.so)
   // gram mode "fast": `gather` points at the pre-split (h, l) f16 words of the factor table
-  // (presplit_f16x2_kernel) and range violations are OR-ed into *fast_flag (bit 0: table, bit 1: ratings)
+  // (presplit_f16x2_kernel) and range violations are OR-ed into *fast_flag (bit 0: table, bit 1: ratings).
+  // fast_words, pre_words, no_pack, whole_only: host-only and no longer read -- Route carries what they said; they stay
+  // until a change of the kernels' argument layout removes them
   int fast_words;
   int* fast_flag;
   // round 6 (kArithPre): `gather` points at the pre-split bf16 h | m | l planes of the factor table (presplit_bf16x3_kernel),
-  // rows of pre_pitch bytes.  1: the production form (packed last block, kArithPrePk), 2: the verification form (kArithPre,
-  // bit-identical to the in-kernel split)
+  // rows of pre_pitch bytes
   int pre_words;
   unsigned pre_pitch;
   // fused train SSE (als.cu:979-991 folded into the Theta update): when not null, every whole-row item of a wave-kernel
@@ -102,8 +103,6 @@ struct KernelArgs {
   // the fp32 gather table itself (`gather` is replaced by the pre-split planes / f16 words of a launch that uses them): what
   // the Gram-free CG of short rows reads (als_short.hip)
   const float* gather_f32;
-  // the six-product forms throughout (CUMF_PRESPLIT_OFF / CUMF_PRESPLIT_VERIFY: what the bit-identity tests compare): no packed
-  // last block in the in-kernel split either (kArithSplitPk, als_wave.hip)
   int no_pack;
 };
 constexpr int kSseBins = 1024;
@@ -127,8 +126,6 @@ struct PlanLists {
 constexpr int kShortRow = 32;
 bool short_cg_available(int f);
 hipError_t launch_short_cg(const KernelArgs& a, long n_items, hipStream_t stream);
-hipError_t launch_half_iteration(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream,
-                                 const PlanLists* lists = nullptr);
 hipError_t launch_solve_batched(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,
                                 hipStream_t stream);
 // Gram arithmetic of the fused / materialising passes.
@@ -140,12 +137,65 @@ hipError_t launch_solve_batched(const float* A, const float* b, float* x, long b
 //               products per fp32 product (22 significand bits); fused LU / CG passes of the wave
 //               kernels only, everything else as kGramAuto; values must stay below 15.99 in magnitude.
 enum { kGramAuto = 0, kGramExact = 1, kGramFast = 2 };
+// Arithmetic of the wave kernels' Gram pass (als_wave.hip, where each form is described): the in-kernel bf16x3 split
+// (kArithSplit3; kArithSplitPk with a rating-only last block packed), the pre-split f16 words of gram mode "fast"
+// (kArithFast), the pre-split bf16 h | m | l planes (kArithPre; kArithPrePk with the last block packed).
+enum { kArithSplit3 = 0, kArithFast = 1, kArithPre = 2, kArithPrePk = 3, kArithSplitPk = 4 };
+
+// ---- Routing of a half-iteration (als_route.cpp): which kernels, arithmetic and solvers a call runs on.
+// Every run-time knob that routes, read in one place.  gram / presplit: the environment (CUMF_ALS_GRAM,
+// CUMF_ALS_PRESPLIT) on first use, then what cumf_set_gram_mode / cumf_set_presplit set; presplit_mb, splitpk,
+// short_cg: the environment once per process; batched, wave_solve, lu_exact: the environment on every call.
+struct Switches {
+  int gram;            // kGram*                       CUMF_ALS_GRAM = exact | fast | (split)
+  int presplit;        // CUMF_PRESPLIT_*              CUMF_ALS_PRESPLIT = 0 | 1 | 2
+  double presplit_mb;  // auto pre-split table cap     CUMF_ALS_PRESPLIT_MB (64)
+  bool splitpk;        // kArithSplitPk wanted         CUMF_ALS_SPLITPK=0 turns it off
+  bool short_cg;       // Gram-free CG of short rows   CUMF_ALS_SHORT_CG=0 turns it off
+  bool batched;        // two-wave path (f >= 112)     CUMF_ALS_NO_BATCHED turns it off
+  bool wave_solve;     // wave CG of chunked rows      CUMF_ALS_NO_WAVE_SOLVE turns it off
+  bool lu_exact;       // oracle-order batched LU      CUMF_ALS_LU_EXACT=1
+};
+Switches switches();
 void set_gram_mode(int mode);
-int gram_mode();
-bool wave_path_available(int f, int mode);
-// the f >= 112 path: two waves per item form the Gram; whole rows are solved in place (CG always, LU up to NB = 9),
-// larger LUs and the materialising pass go Gram -> tiles (dense slots of the pooled tile buffer) -> reduce kernel
-bool wave_batched_path(int f, int mode);
+void set_presplit_mode(int mode);
+
+// The facts of a plan the route depends on (all zero: the route of (f, mode) alone, e.g. cumf_fused_available).
+struct PlanFacts {
+  int nb;
+  long n_mrows, n_citems, n_witems;
+  double chunk_share;  // share of the plan's ratings that sits in chunked rows
+  long n_short;        // whole rows of at most kShortRow ratings (the last items)
+  long gather_rows;    // rows of the gather table (cumf_plan_set_gather_rows), 0: unknown
+};
+enum Path {
+  kPathNone,       // no fused kernel for (f, solver)
+  kPathGeneric,    // f > kMaxF, materialise only: the plain kernels of als_generic.hip
+  kPathWorkgroup,  // als_item_kernel + als_reduce_kernel (f <= 14, gram mode exact)
+  kPathOneWave,    // als_wave_kernel, one wave per item (16 <= f <= 111)
+  kPathTwoWave,    // als_wave_multi_kernel, two waves per item, chunked rows and tiles batched apart (112 <= f <= 207)
+};
+enum Table { kTableNone, kTablePlanes, kTableF16Words };  // what the call prepares from the gather table
+enum Solve {
+  kSolveInKernel,    // by the wave(s) that formed the Gram
+  kSolveTileBuffer,  // Gram dumped to the dense slots of the pooled tile buffer, then als_reduce_kernel
+  kSolveReduce,      // als_reduce_kernel (the workgroup solvers) on the plan's slots
+  kSolveWaveCG,      // als_wave_cg_kernel on the plan's slots
+};
+struct Route {
+  Path path;
+  int arith;         // kArith* of the wave kernels
+  int fc;            // 100: the f = 100 instances of NB = 7 (the reference's get_hermitian100), else 0
+  Table table;
+  bool chunk_first;  // one-wave LU: the chunk items in a launch of their own, the whole rows on the instance without dumps
+  long n_short;      // CG: the last n_short items go to the Gram-free CG (als_short.hip)
+  Solve chunked;     // solver of the chunked rows
+  Solve whole;       // solver of the whole rows
+  bool sse;          // cumf_als_update_fused_sse covers every row
+};
+Route route_for(int f, int mode, const PlanFacts& plan, const Switches& sw);
+hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& lists, hipStream_t stream);
+
 // unpack = 0: full (batch x f x f) -> packed (batch x f(f+1)/2); unpack = 1: `full` is the packed input,
 // `packed` receives the mirrored full matrices
 hipError_t launch_presplit(const float* src, unsigned* dst, size_t n, int* flag, hipStream_t stream);

@@ -42,12 +42,9 @@ namespace cumf {
 // feature-block count) plus once with -DCUMF_NB_SLICE=0 (dispatch, NB-independent kernels,
 // shared state), so that the build runs in parallel; without the macro everything lands in
 // one translation unit.
-#ifndef CUMF_ONLY_NB
-#define CUMF_ONLY_NB 0  // experiments (tools/lu_variants.sh): build the kernels of one NB only
-#endif
 #if !defined(CUMF_NB_SLICE)
 #define CUMF_SLICE_COMMON 1
-#define CUMF_SLICE_HAS(n) (CUMF_ONLY_NB == 0 || CUMF_ONLY_NB == (n))
+#define CUMF_SLICE_HAS(n) 1
 #elif CUMF_NB_SLICE == 0
 #define CUMF_SLICE_COMMON 1
 #define CUMF_SLICE_HAS(n) 0
@@ -57,17 +54,9 @@ namespace cumf {
 #endif
 
 
-#ifndef CUMF_LU_MFMA
-#define CUMF_LU_MFMA 1  // 0: fused LU through the LDS hand-over + lu_solve_reg (the previous path)
-#endif
 // The accumulator LU pays off from f = 96 on (measured: f = 64 18.8 vs 18.0 ms, f = 10 0.67 vs 0.56 ms with
 // the thread-grid LU; f = 100 35.7 vs 36.8, f = 128 62.2 vs 63.8, f = 200 200 vs 224).
-constexpr bool lu_on_accumulators(int nb) { return CUMF_LU_MFMA != 0 && nb >= 7; }
-#ifndef CUMF_RR_TILES
-#define CUMF_RR_TILES 1
-#endif
-constexpr bool kRoundRobinTiles = CUMF_RR_TILES != 0;
-static_assert(kRoundRobinTiles || !CUMF_LU_MFMA, "lu_solve_mfma (als_lu_wg.h) assumes round-robin tiles");
+constexpr bool lu_on_accumulators(int nb) { return nb >= 7; }
 
 
 
@@ -87,7 +76,7 @@ struct Geo {
   // last role owns the tiles that stay live to the end); the price is that every role reads all
   // NB feature blocks in the Gram pass.
   __host__ __device__ static constexpr int tile(int W, int s) {
-    return (kRoundRobinTiles && NB >= 7) ? W + 4 * s : W * TPW + s;
+    return NB >= 7 ? W + 4 * s : W * TPW + s;
   }
 };
 
@@ -565,7 +554,7 @@ __device__ __forceinline__ void lu_solve_lds(float* __restrict__ G, int ldg, int
 //   2. every thread reads row k at its own row / column positions and applies
 //      a_ij -= (u_ki / u_kk) * u_kj  to its registers (i > k).
 // This is Gaussian elimination without pivoting restricted to the upper triangle (U = D L^T of
-// A = L U).  Tried and measured slower or equal (tools/lu_variants.sh): panels of 2 or 4
+// A = L U).  Tried and measured slower or equal: panels of 2 or 4
 // pivots per barrier with a redundant in-register panel elimination (half / quarter the
 // barriers, same LDS reads: equal at M = 2, spills at M = 4), a rolled pivot loop (+5 %).
 // U may alias the memory `load` reads from: all loads complete before the first publish.
@@ -1287,8 +1276,7 @@ static hipError_t launch_nb(const KernelArgs& a, long n_items, long n_mrows, hip
     const size_t solve = MODE == kModeLU ? lu_fused_lds_floats<NB>(a.f) : solve_lds_floats(a.f, MODE);
     floats = floats > solve ? floats : solve;
   }
-  static const size_t lds_pad = getenv("CUMF_ALS_LDS_PAD") ? (size_t)atol(getenv("CUMF_ALS_LDS_PAD")) : 0;  // occupancy experiments
-  const size_t lds = floats * sizeof(float) + lds_pad;
+  const size_t lds = floats * sizeof(float);
   hipError_t e;
   if (lds > 64 * 1024) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(als_item_kernel<NB, VT, MODE>),
@@ -1298,24 +1286,18 @@ static hipError_t launch_nb(const KernelArgs& a, long n_items, long n_mrows, hip
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  timing_begin();
-  if (g_timing) (void)hipEventRecord(g_ev[0], stream);
-  g_timed_item = n_items > 0;
-  g_timed_reduce = n_mrows > 0;
   if (n_items > 0) {
     note_item_kernel(reinterpret_cast<const void*>(als_item_kernel<NB, VT, MODE>));
     hipLaunchKernelGGL((als_item_kernel<NB, VT, MODE>), dim3((unsigned)n_items), dim3(kThreads), lds, stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  if (g_timing) (void)hipEventRecord(g_ev[1], stream);
   if (n_mrows > 0) {
     const size_t lds2 = (MODE == kModeMaterialize) ? 0 : lds;
     hipLaunchKernelGGL((als_reduce_kernel<NB, MODE>), dim3((unsigned)n_mrows), dim3(kThreads), lds2, stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  if (g_timing) (void)hipEventRecord(g_ev[2], stream);
   return hipSuccess;
 }
 
@@ -1355,31 +1337,26 @@ static hipError_t launch_solve_nb(const float* A, const float* b, float* x, long
 }
 
 // wave-per-item kernels (als_wave.hip), one translation unit per NB
+// whole: every item of the launch is a whole row (the LU instance without the dump exit)
 template <int NB>
-hipError_t wave_item_launch(const KernelArgs& a, int mode, long n_items, hipStream_t stream);
+hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream);
 template <int NB>
 hipError_t wave_solve_launch(const KernelArgs& a, int mode, long n_rows, hipStream_t stream);
-#define CUMF_DECLARE_WAVE(N)                                                                       \
-  template <>                                                                                      \
-  hipError_t wave_item_launch<N>(const KernelArgs& a, int mode, long n_items, hipStream_t stream); \
-  template <>                                                                                      \
+#define CUMF_DECLARE_WAVE(N)                                                                                                \
+  template <>                                                                                                               \
+  hipError_t wave_item_launch<N>(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream); \
+  template <>                                                                                                               \
   hipError_t wave_solve_launch<N>(const KernelArgs& a, int mode, long n_rows, hipStream_t stream);
 CUMF_DECLARE_WAVE(2) CUMF_DECLARE_WAVE(3) CUMF_DECLARE_WAVE(4) CUMF_DECLARE_WAVE(5)
 CUMF_DECLARE_WAVE(6) CUMF_DECLARE_WAVE(7) CUMF_DECLARE_WAVE(8) CUMF_DECLARE_WAVE(9) CUMF_DECLARE_WAVE(10)
 CUMF_DECLARE_WAVE(11) CUMF_DECLARE_WAVE(12) CUMF_DECLARE_WAVE(13)
 
-// reduce kernel of the chunked rows on its own (the items came from the wave-per-item kernel)
+// solver of the chunked rows on its own (the items came from the wave kernels): Route::chunked
 template <int NB>
-static hipError_t launch_reduce_only(const KernelArgs& a, int mode, long n_mrows, hipStream_t stream) {
+static hipError_t launch_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream) {
   if (n_mrows <= 0) return hipSuccess;
   if constexpr (NB >= 2) {
-    if (gram_mode() != kGramExact && !getenv("CUMF_ALS_NO_WAVE_SOLVE")) {
-      // CG on the tiles at wave level: the chunked rows of the wave kernels (NB <= 7) and the systems too
-      // large for the LDS-resident 4-wave CG (f > 128; two waves share the tiles).  NB = 8, 9 (f = 112 ..
-      // 128) stay on the 4-wave solvers: measured 38.8 vs 56.3 ms (CG) and 49.0 vs 62.2 ms (LU) per Netflix
-      // iteration at f = 128 -- one wave holding 45 tiles spills and has nobody to overlap with.
-      if (mode == kModeCG && (NB <= kMaxWaveNB || a.f > kVecLd)) return wave_solve_launch<NB>(a, mode, n_mrows, stream);
-    }
+    if (r.chunked == kSolveWaveCG) return wave_solve_launch<NB>(a, mode, n_mrows, stream);
   }
   if (mode == kModeMaterialize) {
     hipLaunchKernelGGL((als_reduce_kernel<NB, kModeMaterialize>), dim3((unsigned)n_mrows), dim3(kThreads), 0, stream, a);
@@ -1408,7 +1385,7 @@ static hipError_t launch_reduce_only(const KernelArgs& a, int mode, long n_mrows
   return hipGetLastError();
 }
 template <int NB>
-hipError_t slice_reduce_only(const KernelArgs& a, int mode, long n_mrows, hipStream_t stream);
+hipError_t slice_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream);
 
 
 // Large systems (f >= 112): the Gram of every row is dumped as accumulator tiles (two waves per item,
@@ -1417,7 +1394,7 @@ hipError_t slice_reduce_only(const KernelArgs& a, int mode, long n_mrows, hipStr
 // in device memory, separate solver", als.cu:782-831), with tiles instead of full f x f matrices and
 // in batches of the pooled tile buffer (als_plan.cpp: up to 48 GiB, usually ONE batch).
 template <int NB>
-static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const PlanLists& L, hipStream_t stream) {
+static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
   if constexpr (NB < 2) {
     return hipErrorInvalidValue;
   } else {
@@ -1430,16 +1407,13 @@ static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const PlanLi
     a.item_len = L.c_len;
     a.item_slot = L.c_slot;
     a.item_rowlen = L.c_rowlen;
-    e = wave_item_launch<NB>(a, kModeLU, L.n_citems, stream);  // every item has a slot: nothing is solved in place
+    e = wave_item_launch<NB>(a, kModeLU, r, false, L.n_citems, stream);  // every item has a slot: nothing is solved in place
     if (e != hipSuccess) return e;
-    e = launch_reduce_only<NB>(a0, mode, L.n_mrows, stream);
+    e = launch_reduce_only<NB>(a0, mode, r, L.n_mrows, stream);
     if (e != hipSuccess) return e;
   }
-  // 2. whole rows.  CG, and LU up to NB = 9: solved by the two waves that formed the Gram, in one launch.
-  // Larger LUs go on through the tile buffer: two waves on a 200 x 200 elimination (one wave per SIMD, a
-  // barrier per panel) lose more than the round trip costs (Netflix f = 200: 112 vs 106 ms, f = 160: 85
-  // vs 78; f = 128: 39.0 vs 41.6 the other way).
-  if (mode == kModeCG || (mode == kModeLU && NB <= kMaxFusedLuWaveNB)) {
+  // 2. whole rows: solved by the two waves that formed the Gram, in one launch, or through the tile buffer
+  if (r.whole == kSolveInKernel) {
     if (L.n_witems <= 0) return hipSuccess;
     KernelArgs a = a0;
     a.item_row = L.w_row;
@@ -1448,7 +1422,7 @@ static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const PlanLi
     a.item_rowlen = L.w_rowlen;
     a.item_slot = nullptr;  // no slots: nothing is dumped
     a.dense_slots = 0;
-    return wave_item_launch<NB>(a, mode, L.n_witems, stream);
+    return wave_item_launch<NB>(a, mode, r, false, L.n_witems, stream);
   }
   // large LU / materialise (cumf_get_hermitian): in batches of part2_rows dense slots
   for (long w0 = 0; w0 < L.n_witems; w0 += L.part2_rows) {
@@ -1463,16 +1437,16 @@ static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const PlanLi
     a.part = L.part2;
     a.mrow_row = L.w_row + w0;
     a.mrow_rowlen = L.w_rowlen + w0;
-    e = wave_item_launch<NB>(a, kModeLU, cnt, stream);
+    e = wave_item_launch<NB>(a, kModeLU, r, false, cnt, stream);
     if (e != hipSuccess) return e;
-    e = launch_reduce_only<NB>(a, mode, cnt, stream);
+    e = launch_reduce_only<NB>(a, mode, r, cnt, stream);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
   }
 }
 template <int NB>
-hipError_t slice_batched(const KernelArgs& a, int mode, const PlanLists& L, hipStream_t stream);
+hipError_t slice_batched(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream);
 
 // Per-NB entry points (one translation unit each, see CUMF_NB_SLICE above).
 template <int NB>
@@ -1488,26 +1462,9 @@ hipError_t slice_solve(const float* A, const float* b, float* x, long batch, int
   hipError_t slice_solve<N>(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters, \
                             hipStream_t stream);                                                                 \
   template <>                                                                                                    \
-  hipError_t slice_reduce_only<N>(const KernelArgs& a, int mode, long n_mrows, hipStream_t stream);              \
+  hipError_t slice_reduce_only<N>(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream); \
   template <>                                                                                                    \
-  hipError_t slice_batched<N>(const KernelArgs& a, int mode, const PlanLists& L, hipStream_t stream);
-#define CUMF_STUB_SLICE(N)                                                                                       \
-  template <>                                                                                                    \
-  hipError_t slice_half_iteration<N>(const KernelArgs&, int, long, long, hipStream_t) {                          \
-    return hipErrorInvalidValue;                                                                                 \
-  }                                                                                                              \
-  template <>                                                                                                    \
-  hipError_t slice_solve<N>(const float*, const float*, float*, long, int, int, int, hipStream_t) {              \
-    return hipErrorInvalidValue;                                                                                 \
-  }                                                                                                              \
-  template <>                                                                                                    \
-  hipError_t slice_reduce_only<N>(const KernelArgs&, int, long, hipStream_t) {                                   \
-    return hipErrorInvalidValue;                                                                                 \
-  }                                                                                                              \
-  template <>                                                                                                    \
-  hipError_t slice_batched<N>(const KernelArgs&, int, const PlanLists&, hipStream_t) {                           \
-    return hipErrorInvalidValue;                                                                                 \
-  }
+  hipError_t slice_batched<N>(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream);
 #define CUMF_DEFINE_SLICE(N)                                                                                     \
   template <>                                                                                                    \
   hipError_t slice_half_iteration<N>(const KernelArgs& a, int mode, long n_items, long n_mrows,                 \
@@ -1525,12 +1482,12 @@ hipError_t slice_solve(const float* A, const float* b, float* x, long batch, int
     return launch_solve_nb<N, kModeLU>(A, b, x, batch, f, cg_iters, stream);                                     \
   }                                                                                                              \
   template <>                                                                                                    \
-  hipError_t slice_reduce_only<N>(const KernelArgs& a, int mode, long n_mrows, hipStream_t stream) {             \
-    return launch_reduce_only<N>(a, mode, n_mrows, stream);                                                      \
+  hipError_t slice_reduce_only<N>(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream) { \
+    return launch_reduce_only<N>(a, mode, r, n_mrows, stream);                                                   \
   }                                                                                                              \
   template <>                                                                                                    \
-  hipError_t slice_batched<N>(const KernelArgs& a, int mode, const PlanLists& L, hipStream_t stream) {           \
-    return launch_batched_nb<N>(a, mode, L, stream);                                                             \
+  hipError_t slice_batched<N>(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) { \
+    return launch_batched_nb<N>(a, mode, r, L, stream);                                                          \
   }
 
 CUMF_DECLARE_SLICE(1) CUMF_DECLARE_SLICE(2) CUMF_DECLARE_SLICE(3) CUMF_DECLARE_SLICE(4) CUMF_DECLARE_SLICE(5)
@@ -1538,183 +1495,128 @@ CUMF_DECLARE_SLICE(6) CUMF_DECLARE_SLICE(7) CUMF_DECLARE_SLICE(8) CUMF_DECLARE_S
 CUMF_DECLARE_SLICE(11) CUMF_DECLARE_SLICE(12) CUMF_DECLARE_SLICE(13)
 #if CUMF_SLICE_HAS(1)
 CUMF_DEFINE_SLICE(1)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(1)
 #endif
 #if CUMF_SLICE_HAS(2)
 CUMF_DEFINE_SLICE(2)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(2)
 #endif
 #if CUMF_SLICE_HAS(3)
 CUMF_DEFINE_SLICE(3)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(3)
 #endif
 #if CUMF_SLICE_HAS(4)
 CUMF_DEFINE_SLICE(4)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(4)
 #endif
 #if CUMF_SLICE_HAS(5)
 CUMF_DEFINE_SLICE(5)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(5)
 #endif
 #if CUMF_SLICE_HAS(6)
 CUMF_DEFINE_SLICE(6)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(6)
 #endif
 #if CUMF_SLICE_HAS(7)
 CUMF_DEFINE_SLICE(7)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(7)
 #endif
 #if CUMF_SLICE_HAS(8)
 CUMF_DEFINE_SLICE(8)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(8)
 #endif
 #if CUMF_SLICE_HAS(9)
 CUMF_DEFINE_SLICE(9)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(9)
 #endif
 #if CUMF_SLICE_HAS(10)
 CUMF_DEFINE_SLICE(10)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(10)
 #endif
 #if CUMF_SLICE_HAS(11)
 CUMF_DEFINE_SLICE(11)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(11)
 #endif
 #if CUMF_SLICE_HAS(12)
 CUMF_DEFINE_SLICE(12)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(12)
 #endif
 #if CUMF_SLICE_HAS(13)
 CUMF_DEFINE_SLICE(13)
-#elif CUMF_ONLY_NB != 0
-CUMF_STUB_SLICE(13)
 #endif
 
 #if CUMF_SLICE_COMMON
 #define CUMF_NB_CASE(N, call) case N: return call;
 
-static int g_gram_mode = -1;
-void set_gram_mode(int mode) { g_gram_mode = (mode == kGramExact || mode == kGramFast) ? mode : kGramAuto; }
-int gram_mode() {
-  if (g_gram_mode < 0) {
-    const char* e = getenv("CUMF_ALS_GRAM");  // exact | fast | split (default)
-    g_gram_mode = (e && (e[0] == 'e' || e[0] == 'E')) ? kGramExact : (e && (e[0] == 'f' || e[0] == 'F')) ? kGramFast : kGramAuto;
-  }
-  return g_gram_mode;
-}
-bool wave_path_available(int f, int mode) {
-  // NB = 1 (f <= 14: one tile, a 32-rating MFMA K and one wave per row are all overhead) stays on the
-  // workgroup kernels: measured 0.56 vs 3.4 ms per iteration at f = 10, while f = 20 .. 48 is 1.4-1.7x
-  // faster on the wave kernels
-  return gram_mode() != kGramExact && nb_for_f(f) >= 2 && nb_for_f(f) <= kMaxWaveNB &&
-         (mode == kModeLU || mode == kModeMaterialize || mode == kModeCG);
-}
-
-bool wave_batched_path(int f, int mode) {
-  if (gram_mode() == kGramExact || getenv("CUMF_ALS_NO_BATCHED")) return false;
-  const int nb = nb_for_f(f);
-  // f >= 112 (NB 8 .. 13): two waves per item form the Gram, a solver kernel picks the tiles up
-  // (f <= 111: everything runs inside the wave-per-item kernel, see wave_path_available)
-  return nb > kMaxWaveNB && nb <= nb_for_f(kMaxF) && (mode == kModeLU || mode == kModeMaterialize || mode == kModeCG);
-}
-
-hipError_t launch_half_iteration(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream,
-                                 const PlanLists* lists) {
-  if (lists != nullptr && wave_batched_path(a.f, mode)) {
-    timing_begin();
-    if (g_timing) (void)hipEventRecord(g_ev[0], stream);
-    g_timed_item = true;
-    g_timed_reduce = false;
-    hipError_t e = hipErrorInvalidValue;
-    switch (nb_for_f(a.f)) {
-#define CUMF_BATCHED(N) case N: e = slice_batched<N>(a, mode, *lists, stream); break;
-      CUMF_BATCHED(8) CUMF_BATCHED(9) CUMF_BATCHED(10) CUMF_BATCHED(11) CUMF_BATCHED(12) CUMF_BATCHED(13)
-#undef CUMF_BATCHED
-      default: break;
-    }
-    if (g_timing) {
-      (void)hipEventRecord(g_ev[1], stream);
-      (void)hipEventRecord(g_ev[2], stream);
-    }
-    return e;
-  }
-  if (wave_path_available(a.f, mode)) {
-    timing_begin();
-    if (g_timing) (void)hipEventRecord(g_ev[0], stream);
-    g_timed_item = n_items > 0;
-    g_timed_reduce = n_mrows > 0;
-    hipError_t e = hipSuccess;
-    KernelArgs aw = a;
-    aw.whole_only = n_mrows == 0;  // no chunked row in the plan: every item is a whole row
-    // A plan with a FEW chunked rows (a Theta side with a handful of very long columns): their chunk items go first, in a
-    // launch of their own, and the whole rows keep the instance without the dump exit (no spilled accumulators, VERDICT r03
-    // weak 7).  When the chunks are most of the work (the Netflix X side: 86 % of the ratings) one combined launch stays:
-    // the whole rows fill the tail of the equal-sized chunk items, worth more than the spills cost.  (Round 5 measured
-    // the alternative for that side too -- the chunk items through the dump-only instance, 0 spilled registers, one after
-    // the other or side by side on a second stream: 6.83 / 6.82 ms against 6.69-6.85 combined, same box,
-    // profiles/r05/stage_variants_ab.txt: the 63 spilled registers of the combined instance cost nothing measurable.)
-    KernelArgs ac = a;
-    long n_chunk_first = 0;
-    if (mode == kModeLU && n_mrows > 0 && lists != nullptr && lists->n_citems > 0 && lists->n_witems > 0 &&
-        lists->chunk_share < 0.25) {  // (LU: the only mode with an instance for whole rows alone)
-      n_chunk_first = lists->n_citems;
-      ac.item_row = lists->c_row, ac.item_begin = lists->c_begin, ac.item_len = lists->c_len;
-      ac.item_slot = lists->c_slot, ac.item_rowlen = lists->c_rowlen;
-      ac.whole_only = 0;
-      aw.item_row = lists->w_row, aw.item_begin = lists->w_begin, aw.item_len = lists->w_len;
-      aw.item_slot = nullptr, aw.item_rowlen = lists->w_rowlen;
-      aw.whole_only = 1;
-      n_items = lists->n_witems;
-    }
-    // Round 6: the short whole rows of a CG plan (the last n_short items) never form their Gram matrix (als_short.hip)
-    static const bool short_cg_on = !getenv("CUMF_ALS_SHORT_CG") || atoi(getenv("CUMF_ALS_SHORT_CG")) != 0;
-    long n_short = 0;
-    if (mode == kModeCG && short_cg_on && lists != nullptr && short_cg_available(a.f) && !a.dense_slots) n_short = lists->n_short;
-    KernelArgs as = aw;
-    if (n_short > 0) {
-      n_items -= n_short;
-      as.item_row += n_items, as.item_begin += n_items, as.item_len += n_items, as.item_rowlen += n_items;
-      e = launch_short_cg(as, n_short, stream);  // first: the tail of the long items then fills in behind it
-      if (e != hipSuccess) return e;
-    }
-    switch (nb_for_f(a.f)) {
-#define CUMF_WAVE(N)                                              \
-  case N:                                                         \
-    if (n_chunk_first > 0) {                                      \
-      e = wave_item_launch<N>(ac, mode, n_chunk_first, stream);   \
-      if (e != hipSuccess) return e;                              \
-    }                                                             \
-    e = wave_item_launch<N>(aw, mode, n_items, stream);           \
-    if (e != hipSuccess) return e;                                \
-    if (g_timing) (void)hipEventRecord(g_ev[1], stream);          \
-    e = slice_reduce_only<N>(a, mode, n_mrows, stream);           \
-    break;
-      CUMF_WAVE(2) CUMF_WAVE(3) CUMF_WAVE(4) CUMF_WAVE(5) CUMF_WAVE(6) CUMF_WAVE(7)
-#undef CUMF_WAVE
-      default: return hipErrorInvalidValue;
-    }
-    if (g_timing) (void)hipEventRecord(g_ev[2], stream);
-    return e;
-  }
-#define CUMF_HALF(N) CUMF_NB_CASE(N, slice_half_iteration<N>(a, mode, n_items, n_mrows, stream))
+// the wave kernels of one launch, by NB (als_wave.hip)
+static hipError_t wave_items(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream) {
   switch (nb_for_f(a.f)) {
-    CUMF_HALF(1) CUMF_HALF(2) CUMF_HALF(3) CUMF_HALF(4) CUMF_HALF(5) CUMF_HALF(6) CUMF_HALF(7)
-    CUMF_HALF(8) CUMF_HALF(9) CUMF_HALF(10) CUMF_HALF(11) CUMF_HALF(12) CUMF_HALF(13)
+#define CUMF_WAVE(N) CUMF_NB_CASE(N, wave_item_launch<N>(a, mode, r, whole, n_items, stream))
+    CUMF_WAVE(2) CUMF_WAVE(3) CUMF_WAVE(4) CUMF_WAVE(5) CUMF_WAVE(6) CUMF_WAVE(7)
+#undef CUMF_WAVE
     default: return hipErrorInvalidValue;
   }
+}
+
+// One-wave path: the items of the plan (Route::n_short, Route::chunk_first), then launch_half_iteration's reduce phase
+static hipError_t one_wave_items(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
+  KernelArgs aw = a;
+  long n_items = L.n_items;
+  if (r.chunk_first) {
+    aw.item_row = L.w_row, aw.item_begin = L.w_begin, aw.item_len = L.w_len;
+    aw.item_slot = nullptr, aw.item_rowlen = L.w_rowlen;
+    n_items = L.n_witems;
+  }
+  if (r.n_short > 0) {  // the last items; first: the tail of the long items then fills in behind it
+    n_items -= r.n_short;
+    KernelArgs as = aw;
+    as.item_row += n_items, as.item_begin += n_items, as.item_len += n_items, as.item_rowlen += n_items;
+    hipError_t e = launch_short_cg(as, r.n_short, stream);
+    if (e != hipSuccess) return e;
+  }
+  if (r.chunk_first) {
+    KernelArgs ac = a;
+    ac.item_row = L.c_row, ac.item_begin = L.c_begin, ac.item_len = L.c_len;
+    ac.item_slot = L.c_slot, ac.item_rowlen = L.c_rowlen;
+    hipError_t e = wave_items(ac, mode, r, false, L.n_citems, stream);
+    if (e != hipSuccess) return e;
+  }
+  return wave_items(aw, mode, r, r.chunk_first || L.n_mrows == 0, n_items, stream);
+}
+
+hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
+  const int nb = nb_for_f(a.f);
+  // item phase (event 0 -> 1), then the chunked rows' solver (1 -> 2); the two-wave path interleaves them (item phase only)
+  timing_begin();
+  if (g_timing) (void)hipEventRecord(g_ev[0], stream);
+  g_timed_item = r.path == kPathTwoWave || L.n_items > 0;
+  g_timed_reduce = r.path != kPathTwoWave && L.n_mrows > 0;
+  hipError_t e = hipErrorInvalidValue;
+  bool reduce_done = false;
+  switch (r.path) {
+    case kPathTwoWave:
+      switch (nb) {
+#define CUMF_BATCHED(N) case N: e = slice_batched<N>(a, mode, r, L, stream); break;
+        CUMF_BATCHED(8) CUMF_BATCHED(9) CUMF_BATCHED(10) CUMF_BATCHED(11) CUMF_BATCHED(12) CUMF_BATCHED(13)
+#undef CUMF_BATCHED
+      }
+      reduce_done = true;
+      break;
+    case kPathOneWave: e = one_wave_items(a, mode, r, L, stream); break;
+    case kPathWorkgroup:
+      switch (nb) {
+#define CUMF_HALF(N) case N: e = slice_half_iteration<N>(a, mode, L.n_items, 0, stream); break;
+        CUMF_HALF(1) CUMF_HALF(2) CUMF_HALF(3) CUMF_HALF(4) CUMF_HALF(5) CUMF_HALF(6) CUMF_HALF(7)
+        CUMF_HALF(8) CUMF_HALF(9) CUMF_HALF(10) CUMF_HALF(11) CUMF_HALF(12) CUMF_HALF(13)
 #undef CUMF_HALF
+      }
+      break;
+    default: break;
+  }
+  if (g_timing) (void)hipEventRecord(g_ev[1], stream);
+  if (e == hipSuccess && !reduce_done && L.n_mrows > 0) {
+    switch (nb) {
+#define CUMF_REDUCE(N)                                                                                    \
+  case N:                                                                                                 \
+    e = r.path == kPathOneWave ? slice_reduce_only<N>(a, mode, r, L.n_mrows, stream)                      \
+                               : slice_half_iteration<N>(a, mode, 0, L.n_mrows, stream);                  \
+    break;
+      CUMF_REDUCE(1) CUMF_REDUCE(2) CUMF_REDUCE(3) CUMF_REDUCE(4) CUMF_REDUCE(5) CUMF_REDUCE(6) CUMF_REDUCE(7)
+      CUMF_REDUCE(8) CUMF_REDUCE(9) CUMF_REDUCE(10) CUMF_REDUCE(11) CUMF_REDUCE(12) CUMF_REDUCE(13)
+#undef CUMF_REDUCE
+      default: e = hipErrorInvalidValue;
+    }
+  }
+  if (g_timing) (void)hipEventRecord(g_ev[2], stream);
+  return e;
 }
 
 hipError_t launch_solve_batched(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,

@@ -372,9 +372,8 @@ int fast_flag_get(int** out) {
   return 0;
 }
 
-// Work lists of the batched path; need_tiles: the dense-slot tile buffer (LU above f = 143, materialise at f >= 112).
-// The CG path solves whole rows inside the Gram kernel and needs none.
-int plan_lists(const cumf_plan_t* p, PlanLists* out, hipStream_t stream, bool need_tiles = true) {
+// Work lists of a plan for launch_half_iteration; need_tiles: the dense-slot tile buffer (Route::whole == kSolveTileBuffer).
+int plan_lists(const cumf_plan_t* p, PlanLists* out, hipStream_t stream, bool need_tiles) {
   const size_t tile_bytes = (size_t)p->nb * (p->nb + 1) / 2 * 256 * sizeof(float);
   float* part2 = nullptr;
   long rows = 0;
@@ -418,7 +417,6 @@ int debug_switches() {
 }
 #endif
 
-int presplit_mode();
 KernelArgs base_args(const cumf_plan_t* p, const int* colidx, const float* val, const float* gather, int f,
                      float lambda) {
   KernelArgs a{};
@@ -438,7 +436,6 @@ KernelArgs base_args(const cumf_plan_t* p, const int* colidx, const float* val, 
   a.gather_f32 = gather;
   a.row_begin = p->row_begin;
   a.f = f;
-  a.no_pack = presplit_mode() == CUMF_PRESPLIT_OFF || presplit_mode() == CUMF_PRESPLIT_VERIFY;
   a.lambda = lambda;
 #if CUMF_ABLATE
   a.dbg = debug_switches();
@@ -463,45 +460,24 @@ int fast_words(const cumf_plan_t* p, const float* gather, int f, hipStream_t str
   if (rc) return rc;
   CUMF_HIP_CHECK(launch_presplit(gather, static_cast<unsigned*>(words), n, flag, stream));
   a->gather = reinterpret_cast<const float*>(words);
-  a->fast_words = 1;
   a->fast_flag = flag;
   return 0;
 }
 
-// Round 6 (kArithPre, als_wave.hip): a gather table that lives in the caches -- the Netflix Theta side gathers X (7 MB), the
-// hugewiki X side Theta (16 MB) -- is rewritten per call as bf16 h | m | l planes (1.5 x the bytes, the SAME bits the in-kernel
-// split produces) and the Gram stage takes its MFMA operands from it with 16-byte LDS-DMA + transposing LDS reads instead of
-// ~250 VALU instructions of split per 32 ratings.  An HBM-resident table (the Netflix X side gathers 192 MB of Theta) stays
-// fp32: there the bytes are the roof.  CUMF_ALS_PRESPLIT = 0 never / 1 whenever the shape allows / unset: tables whose
-// planes take at most CUMF_ALS_PRESPLIT_MB (default 64) MB.
-int g_presplit_mode = -2;  // -2: not read yet; CUMF_PRESPLIT_*
-int presplit_mode() {
-  if (g_presplit_mode == -2) {
-    const char* env = getenv("CUMF_ALS_PRESPLIT");
-    g_presplit_mode = (env && env[0] == '0') ? CUMF_PRESPLIT_OFF : (env && env[0] == '1') ? CUMF_PRESPLIT_ON
-                      : (env && env[0] == '2') ? CUMF_PRESPLIT_VERIFY : CUMF_PRESPLIT_AUTO;
-  }
-  return g_presplit_mode;
-}
-bool presplit_wanted(const cumf_plan_t* p, int f, int mode) {
-  static const double cap_mb = getenv("CUMF_ALS_PRESPLIT_MB") ? atof(getenv("CUMF_ALS_PRESPLIT_MB")) : 64.0;
-  const int pm = presplit_mode();
-  if (pm == CUMF_PRESPLIT_OFF) return false;
-  if (gram_mode() != kGramAuto || !(wave_path_available(f, mode) || wave_batched_path(f, mode)) || !presplit_supported(f) ||
-      p->gather_rows <= 0)
-    return false;
-  if (pm == CUMF_PRESPLIT_ON || pm == CUMF_PRESPLIT_VERIFY) return true;
-  return presplit_pays_any_size(f) || (presplit_pays(f) && (double)p->gather_rows * presplit_pitch(f) <= cap_mb * 1048576.0);
-}
+// Round 6 (kArithPre): the gather table as bf16 h | m | l planes, rebuilt per call (als_route.cpp: presplit_wanted).
 int pre_words(const cumf_plan_t* p, const float* gather, int f, hipStream_t stream, KernelArgs* a) {
   void* planes = nullptr;
   const int rc = scratch_get(stream, kScratchPlanes, (size_t)p->gather_rows * presplit_pitch(f), &planes);
   if (rc) return rc;
   CUMF_HIP_CHECK(launch_presplit3(gather, planes, p->gather_rows, f, stream));
   a->gather = reinterpret_cast<const float*>(planes);
-  a->pre_words = presplit_mode() == CUMF_PRESPLIT_VERIFY ? 2 : 1;
   a->pre_pitch = presplit_pitch(f);
   return 0;
+}
+
+PlanFacts plan_facts(const cumf_plan_t* p) {
+  return PlanFacts{p->nb, p->n_mrows, p->n_citems, p->n_witems,
+                   p->plan_nnz > 0 ? (double)p->chunk_nnz / (double)p->plan_nnz : 0.0, p->n_short, p->gather_rows};
 }
 
 thread_local int g_last_error = 0;  // per host thread: concurrent doALS calls do not see each other's state
@@ -597,12 +573,11 @@ extern "C" int cumf_last_kernel_name(char* buf, int cap) {
   return 0;
 }
 
-// Can one fused call (RHS + Gram + solve) handle (f, solver)?  The workgroup kernels: CG f <= 128, LU
-// f <= 200; the wave kernels and the tile-batched path (gram mode auto): both solvers up to f = 207.
+// Can one fused call (RHS + Gram + solve) handle (f, solver)?  Even f with a route (route_for, als_route.cpp).
 extern "C" int cumf_fused_available(int f, int solver) {
   const int mode = solver == CUMF_SOLVER_LU ? kModeLU : kModeCG;
-  if (f <= 0 || f > kMaxF || (f % 2) != 0) return 0;
-  return fused_supported(f, mode) || wave_path_available(f, mode) || wave_batched_path(f, mode);
+  if (f <= 0 || (f % 2) != 0) return 0;
+  return route_for(f, mode, PlanFacts{}, switches()).path != kPathNone;
 }
 
 namespace {
@@ -624,24 +599,13 @@ int update_fused_impl(const cumf_plan_t* p, const int* colidx, const float* val,
   a.cg_iters = cg_iters;
   a.sse_bins = sse_bins;
   const int mode = (solver == CUMF_SOLVER_LU) ? kModeLU : kModeCG;
+  const Route r = route_for(f, mode, plan_facts(p), switches());
   PlanLists lists{};
-  const bool batched = wave_batched_path(f, mode);
-  {
-    // whole rows are solved inside the two-wave Gram kernel (CG always, LU up to NB = 9); only the larger LUs
-    // go through the dense-slot tile buffer.  The one-wave kernels (f <= 111) use the lists to launch the few chunk
-    // items of a plan apart from its whole rows (launch_half_iteration).
-    const int rc = plan_lists(p, &lists, static_cast<hipStream_t>(stream),
-                              batched && mode == kModeLU && p->nb > kMaxFusedLuWaveNB);
-    if (rc) return rc;
-  }
-  if (gram_mode() == kGramFast && (batched || wave_path_available(f, mode))) {
-    const int rc = fast_words(p, gather, f, static_cast<hipStream_t>(stream), &a);
-    if (rc) return rc;
-  } else if (presplit_wanted(p, f, mode)) {
-    const int rc = pre_words(p, gather, f, static_cast<hipStream_t>(stream), &a);
-    if (rc) return rc;
-  }
-  CUMF_HIP_CHECK(launch_half_iteration(a, mode, p->n_items, p->n_mrows, static_cast<hipStream_t>(stream), &lists));
+  int rc = plan_lists(p, &lists, static_cast<hipStream_t>(stream), r.whole == kSolveTileBuffer);
+  if (!rc && r.table == kTableF16Words) rc = fast_words(p, gather, f, static_cast<hipStream_t>(stream), &a);
+  if (!rc && r.table == kTablePlanes) rc = pre_words(p, gather, f, static_cast<hipStream_t>(stream), &a);
+  if (rc) return rc;
+  CUMF_HIP_CHECK(launch_half_iteration(a, mode, r, lists, static_cast<hipStream_t>(stream)));
   return 0;
 }
 }  // namespace
@@ -651,26 +615,11 @@ extern "C" int cumf_als_update_fused(const cumf_plan_t* p, const int* colidx, co
   return update_fused_impl(p, colidx, val, gather, update, f, lambda, solver, cg_iters, nullptr, stream);
 }
 
-// Can the half-iteration of this plan also deliver the train SSE of its rows (cumf_als_update_fused_sse)?  Wherever the
-// wave kernels' solvers run (16 <= f <= 207, gram mode not "exact"), whole rows and chunked rows alike, with two gaps -- the
-// chunked rows of LU plans below f = 96 and of CG plans at f = 112 .. 128 go to the older workgroup solvers (the matrix
-// below spells out which solver takes which rows).
+// Can the half-iteration of this plan also deliver the train SSE of its rows (cumf_als_update_fused_sse)?  Where every
+// solver on its route adds it (Route::sse; route_for spells out the two gaps).
 extern "C" int cumf_fused_sse_available(const cumf_plan_t* p, int solver) {
   if (!p) return 0;
-  const int mode = solver == CUMF_SOLVER_LU ? kModeLU : kModeCG;
-  if (mode == kModeLU) {
-    // whole rows: lu_wave_blocked (f <= 111) / lu_solve_mfma with two wave roles in place (f = 112 .. 143) or with four
-    // from the tile buffer (f >= 144); chunked rows: als_reduce_kernel, whose LU is lu_solve_mfma from NB = 7 on (below
-    // that the thread-grid LU of the packed row store: not covered)
-    if (wave_path_available(p->f, mode)) return p->n_mrows == 0 || p->nb >= 7;
-    return wave_batched_path(p->f, mode);
-  }
-  // CG: every solve of the wave kernels runs cg_wave_core -- one wave per row (f <= 111, chunked rows included:
-  // als_wave_cg_kernel), the two-wave kernel (f >= 112) for whole rows, als_wave_cg_kernel with four waves for chunked rows
-  // above f = 128.  Chunked rows at f = 112 .. 128 go to the LDS-resident four-wave CG of als_reduce_kernel: not covered.
-  if (wave_path_available(p->f, mode)) return 1;
-  if (wave_batched_path(p->f, mode)) return p->n_mrows == 0 || p->f > kVecLd;
-  return 0;
+  return route_for(p->f, solver == CUMF_SOLVER_LU ? kModeLU : kModeCG, plan_facts(p), switches()).sse;
 }
 
 // cumf_als_update_fused + the train SSE of the updated rows for free (als.cu:979-991 folded into the update, see
@@ -700,7 +649,8 @@ int get_hermitian_any(const char* who, const cumf_plan_t* p, const int* colidx, 
   a.tt_half = storage == 1;
   a.tt_packed = storage == 2;
   a.rhs = rhs;
-  if (f > kMaxF) {  // above the tile kernels' range: the plain kernel of als_generic.hip, fp32 f x f storage only
+  const Route r = route_for(f, kModeMaterialize, plan_facts(p), switches());
+  if (r.path == kPathGeneric) {  // above the tile kernels' range: the plain kernel of als_generic.hip, fp32 f x f storage only
     if (storage != 0) {
       fprintf(stderr, "%s: f = %d is above the tile kernels' range (%d): only the fp32 f x f batch (cumf_get_hermitian)\n", who, f, kMaxF);
       return (int)hipErrorInvalidValue;
@@ -709,13 +659,9 @@ int get_hermitian_any(const char* who, const cumf_plan_t* p, const int* colidx, 
     return 0;
   }
   PlanLists lists{};
-  const bool batched = wave_batched_path(f, kModeMaterialize);
-  if (batched) {
-    const int rc = plan_lists(p, &lists, static_cast<hipStream_t>(stream));
-    if (rc) return rc;
-  }
-  CUMF_HIP_CHECK(launch_half_iteration(a, kModeMaterialize, p->n_items, p->n_mrows, static_cast<hipStream_t>(stream),
-                                       batched ? &lists : nullptr));
+  const int rc = plan_lists(p, &lists, static_cast<hipStream_t>(stream), r.whole == kSolveTileBuffer);
+  if (rc) return rc;
+  CUMF_HIP_CHECK(launch_half_iteration(a, kModeMaterialize, r, lists, static_cast<hipStream_t>(stream)));
   return 0;
 }
 }  // namespace
@@ -767,8 +713,7 @@ extern "C" int cumf_lu_solve_batched(const float* A, const float* b, float* x, l
   }
   // CUMF_ALS_LU_EXACT=1: the LDS-resident elimination in the oracle's exact operation order
   // (bit-identical to oracle_lu); default: the register-resident symmetric elimination.
-  const char* ex = getenv("CUMF_ALS_LU_EXACT");
-  const int mode = (ex && atoi(ex) != 0) ? kModeLUExact : kModeLU;
+  const int mode = switches().lu_exact ? kModeLUExact : kModeLU;
   CUMF_HIP_CHECK(launch_solve_batched(A, b, x, batch, f, mode, 0, static_cast<hipStream_t>(stream)));
   return 0;
 }
@@ -805,8 +750,8 @@ extern "C" int cumf_check_gather_table(long gather_rows, int f, int solver, int 
   const int mode = materialize ? kModeMaterialize : (solver == CUMF_SOLVER_LU ? kModeLU : kModeCG);
   if (gather_rows < 0 || f <= 0) return (int)hipErrorInvalidValue;
   if (f > kMaxF) return 0;  // als_generic.hip: 64-bit gather addresses
-  if (wave_path_available(f, mode)) return 0;
-  if (nb_for_f(f) > kMaxWaveNB && wave_batched_path(f, mode)) return 0;  // two-waves-per-item Gram: 64-bit addresses too
+  const Path path = route_for(f, mode, PlanFacts{}, switches()).path;
+  if (path == kPathOneWave || path == kPathTwoWave) return 0;  // the wave kernels: 64-bit addresses too
   const unsigned long long bytes = (unsigned long long)gather_rows * (unsigned long long)f * 4ull;
   if (bytes >= (1ull << 32)) {
     fprintf(stderr,
@@ -824,15 +769,15 @@ extern "C" int cumf_set_gram_mode(int mode) {
   set_gram_mode(mode);
   return 0;
 }
-extern "C" int cumf_get_gram_mode(void) { return gram_mode(); }
+extern "C" int cumf_get_gram_mode(void) { return switches().gram; }
 
 extern "C" int cumf_set_presplit(int mode) {
   if (mode != CUMF_PRESPLIT_AUTO && mode != CUMF_PRESPLIT_OFF && mode != CUMF_PRESPLIT_ON && mode != CUMF_PRESPLIT_VERIFY)
     return (int)hipErrorInvalidValue;
-  g_presplit_mode = mode;
+  set_presplit_mode(mode);
   return 0;
 }
-extern "C" int cumf_get_presplit(void) { return presplit_mode(); }
+extern "C" int cumf_get_presplit(void) { return switches().presplit; }
 extern "C" long cumf_presplit_pitch(int f) { return presplit_supported(f) ? (long)presplit_pitch(f) : 0; }
 extern "C" int cumf_presplit_table(const float* table, void* planes, long rows, int f, void* stream) {
   if (!table || !planes || rows < 0 || !presplit_supported(f)) return (int)hipErrorInvalidValue;

@@ -97,8 +97,7 @@ __device__ __forceinline__ f32x4 mfma_f16(u32x4 a, u32x4 b, f32x4 c) {
 // h | m | l planes as 16-bit arrays): the rows are copied into LDS by 16-byte LDS-DMA and the MFMA operands come out of
 // ds_read_b64_tr_b16, the 16-bit transposing read of gfx950 -- no split, no pack, no select on the VALU.  For gather
 // tables that live in the caches (the Netflix Theta side: X = 7 MB; the hugewiki X side: Theta = 16 MB); an HBM-resident
-// table stays fp32 (1.5 x the bytes would cost more than the VALU work saves).
-enum { kArithSplit3 = 0, kArithFast = 1, kArithPre = 2, kArithPrePk = 3, kArithSplitPk = 4 };
+// table stays fp32 (1.5 x the bytes would cost more than the VALU work saves).  (The kArith* enum: als_internal.h.)
 // kArithSplitPk (round 6): the in-kernel split with the last block PACKED, for f % 16 == 0 -- there the last feature block holds
 // nothing but the rating slot, and six products per tile of its column (four on its diagonal tile) multiply 15 zero columns.
 // The rating is loaded by the lanes of columns 0, 1, 2, split like a feature, and lane c keeps plane c: the packed operand
@@ -2266,7 +2265,7 @@ __global__ __launch_bounds__(64 * NW, NB >= 10 ? 1 : 2) void als_wave_multi_kern
 #define CUMF_WAVE_PART 0
 #endif
 template <int NB>
-hipError_t wave_lu_launch(const KernelArgs& a, long n_items, hipStream_t stream);
+hipError_t wave_lu_launch(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream);
 
 #if CUMF_WAVE_PART == 0
 template <int NB>
@@ -2289,16 +2288,34 @@ hipError_t wave_solve_launch<CUMF_WAVE_NB>(const KernelArgs& a, int mode, long n
 #endif  // CUMF_WAVE_PART == 0
 
 
-#if CUMF_WAVE_SPLITPK
-// f % 16 == 0 on the fp32 table: the packed rating block (CUMF_ALS_SPLITPK=0 keeps the six-product form)
-static bool splitpk_wanted(const KernelArgs& a) {
-  static const bool on = [] {
-    const char* e = getenv("CUMF_ALS_SPLITPK");
-    return !(e && *e == '0');
-  }();
-  return on && !a.no_pack && !a.pre_words && !a.fast_words && (a.f & 15) == 0;
-}
+// The one decoder of (Route::arith, Route::fc): go(arith, fc) on the instance this slice has, as std::integral_constants;
+// hipErrorInvalidValue for any combination it has not.  The FC = 100 instances (the reference's own specialisation,
+// get_hermitian100 for f == 100, als.cu:788-817) exist at NB = 7, the pre-split ones at CUMF_WAVE_PRE (one wave) and on
+// two waves (kArithPre only), the packed in-kernel split at CUMF_WAVE_SPLITPK (f % 16 == 0: FC = 0 only).
+template <class Go>
+static hipError_t with_arith(const Route& r, Go&& go) {
+  auto at = [&](auto arith) -> hipError_t {
+    if (r.fc == 0) return go(arith, std::integral_constant<int, 0>{});
+    if constexpr (CUMF_WAVE_NB == 7 && decltype(arith)::value != kArithSplitPk) {
+      if (r.fc == 100) return go(arith, std::integral_constant<int, 100>{});
+    }
+    return hipErrorInvalidValue;
+  };
+  switch (r.arith) {
+    case kArithSplit3: return at(std::integral_constant<int, kArithSplit3>{});
+    case kArithFast: return at(std::integral_constant<int, kArithFast>{});
+#if CUMF_WAVE_PRE || CUMF_WAVE_NB > 7
+    case kArithPre: return at(std::integral_constant<int, kArithPre>{});
 #endif
+#if CUMF_WAVE_PRE
+    case kArithPrePk: return at(std::integral_constant<int, kArithPrePk>{});
+#endif
+#if CUMF_WAVE_SPLITPK
+    case kArithSplitPk: return at(std::integral_constant<int, kArithSplitPk>{});
+#endif
+    default: return hipErrorInvalidValue;
+  }
+}
 
 #if CUMF_WAVE_PART == 1 && CUMF_WAVE_NB <= 7
 // ---- part 1: the LU form of the wave-per-item kernel
@@ -2316,33 +2333,14 @@ static hipError_t launch_wave_lu_w(const KernelArgs& a, long n_items, hipStream_
   hipLaunchKernelGGL((als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>), dim3((unsigned)n_items), dim3(64), lds, stream, a);
   return hipGetLastError();
 }
-template <int NB, int FC, int ARITH>
-static hipError_t launch_wave_lu(const KernelArgs& a, long n_items, hipStream_t stream) {
-  // whole_only: the plan has no chunked rows, no item of this launch dumps partial tiles
-  return (a.whole_only && !a.dense_slots) ? launch_wave_lu_w<NB, FC, ARITH, true>(a, n_items, stream)
-                                           : launch_wave_lu_w<NB, FC, ARITH, false>(a, n_items, stream);
-}
+// whole: no item of this launch dumps partial tiles (WHOLE: the instance without the dump exit)
 template <>
-hipError_t wave_lu_launch<CUMF_WAVE_NB>(const KernelArgs& a, long n_items, hipStream_t stream) {
-#if CUMF_WAVE_NB == 7
-  // the reference's own specialisation: get_hermitian100 for f == 100 (als.cu:788-817)
-  if (a.f == 100)
-    return a.pre_words == 1 ? launch_wave_lu<7, 100, kArithPrePk>(a, n_items, stream)
-           : a.pre_words    ? launch_wave_lu<7, 100, kArithPre>(a, n_items, stream)
-           : a.fast_words   ? launch_wave_lu<7, 100, kArithFast>(a, n_items, stream)
-                            : launch_wave_lu<7, 100, kArithSplit3>(a, n_items, stream);
-#endif
-#if CUMF_WAVE_PRE
-  if (a.pre_words)
-    return a.pre_words == 1 ? launch_wave_lu<CUMF_WAVE_NB, 0, kArithPrePk>(a, n_items, stream)
-                            : launch_wave_lu<CUMF_WAVE_NB, 0, kArithPre>(a, n_items, stream);
-#endif
-  if (a.pre_words) return hipErrorInvalidValue;
-#if CUMF_WAVE_SPLITPK
-  if (splitpk_wanted(a)) return launch_wave_lu<CUMF_WAVE_NB, 0, kArithSplitPk>(a, n_items, stream);
-#endif
-  return a.fast_words ? launch_wave_lu<CUMF_WAVE_NB, 0, kArithFast>(a, n_items, stream)
-                      : launch_wave_lu<CUMF_WAVE_NB, 0, kArithSplit3>(a, n_items, stream);
+hipError_t wave_lu_launch<CUMF_WAVE_NB>(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream) {
+  return with_arith(r, [&](auto arith, auto fc) {
+    constexpr int ARITH = decltype(arith)::value, FC = decltype(fc)::value;
+    return whole ? launch_wave_lu_w<CUMF_WAVE_NB, FC, ARITH, true>(a, n_items, stream)
+                 : launch_wave_lu_w<CUMF_WAVE_NB, FC, ARITH, false>(a, n_items, stream);
+  });
 }
 #endif
 
@@ -2361,70 +2359,40 @@ static hipError_t launch_wave_fc(const KernelArgs& a, int mode, long n_items, hi
       hipLaunchKernelGGL((als_wave_kernel<NB, kModeMaterialize, FC, kArithSplit3>), dim3((unsigned)n_items), dim3(64),
                          stage_lds, stream, a);
     }
-  } else if (mode == kModeCG) {
+  } else {
     note_item_kernel(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeCG, FC, ARITH>));
     hipLaunchKernelGGL((als_wave_kernel<NB, kModeCG, FC, ARITH>), dim3((unsigned)n_items), dim3(64), stage_lds, stream, a);
-  } else {
-    return wave_lu_launch<NB>(a, n_items, stream);  // part 1 of this file (picks FC and the arithmetic itself)
   }
   return hipGetLastError();
 }
 
 template <int NB>
-hipError_t wave_item_launch(const KernelArgs& a, int mode, long n_items, hipStream_t stream);
+hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream);
 template <>
-hipError_t wave_item_launch<CUMF_WAVE_NB>(const KernelArgs& a, int mode, long n_items, hipStream_t stream) {
+hipError_t wave_item_launch<CUMF_WAVE_NB>(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items,
+                                          hipStream_t stream) {
   if (n_items <= 0) return hipSuccess;
+  if (mode != kModeMaterialize && mode != kModeLU && mode != kModeCG) return hipErrorInvalidValue;
 #if CUMF_WAVE_NB > 7
   // two waves per item; items without a slot (whole rows) are solved in the kernel (CG, or the LU of
   // als_lu_wg.h with two wave roles), items with one dump their tiles
-  size_t lds = 2 * wave_stage_lds_floats<CUMF_WAVE_NB>() * sizeof(float);  // double-buffered stages
-  if (lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float) > lds) lds = lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float);
-  auto go = [&](auto kernel) {
+  return with_arith(r, [&](auto arith, auto) -> hipError_t {
+    constexpr int ARITH = decltype(arith)::value;
+    if (ARITH != kArithSplit3 && mode == kModeMaterialize) return hipErrorInvalidValue;
+    // double-buffered stages of dword chunks, or one stage image of the pre-split table shared by the two waves
+    size_t lds = ARITH == kArithPre ? PreGeo2<CUMF_WAVE_NB>::kBytes : 2 * wave_stage_lds_floats<CUMF_WAVE_NB>() * sizeof(float);
+    if (lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float) > lds) lds = lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float);
+    const auto kernel = mode == kModeCG ? als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeCG, ARITH>
+                                        : als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeLU, ARITH>;
     note_item_kernel(reinterpret_cast<const void*>(kernel));
     hipLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(128), lds, stream, a);
-  };
-  if (a.pre_words) {  // the pre-split table (round 6): one shared stage image instead of two buffers of dword chunks
-    if (mode == kModeMaterialize) return hipErrorInvalidValue;
-    lds = PreGeo2<CUMF_WAVE_NB>::kBytes;
-    if (lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float) > lds) lds = lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float);
-    if (mode == kModeCG)
-      go(als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeCG, kArithPre>);
-    else
-      go(als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeLU, kArithPre>);
-  } else if (a.fast_words) {
-    if (mode == kModeMaterialize) return hipErrorInvalidValue;
-    if (mode == kModeCG)
-      go(als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeCG, kArithFast>);
-    else
-      go(als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeLU, kArithFast>);
-  } else if (mode == kModeCG) {
-    go(als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeCG, kArithSplit3>);
-  } else {
-    go(als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeLU, kArithSplit3>);
-  }
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 #else
-  if (mode != kModeMaterialize && mode != kModeLU && mode != kModeCG) return hipErrorInvalidValue;
-#if CUMF_WAVE_NB == 7
-  // the reference's own specialisation: get_hermitian100 for f == 100 (als.cu:788-817)
-  if (a.f == 100)
-    return a.pre_words == 1 ? launch_wave_fc<7, 100, kArithPrePk>(a, mode, n_items, stream)
-           : a.pre_words    ? launch_wave_fc<7, 100, kArithPre>(a, mode, n_items, stream)
-           : a.fast_words   ? launch_wave_fc<7, 100, kArithFast>(a, mode, n_items, stream)
-                            : launch_wave_fc<7, 100, kArithSplit3>(a, mode, n_items, stream);
-#endif
-#if CUMF_WAVE_PRE
-  if (a.pre_words)
-    return a.pre_words == 1 ? launch_wave_fc<CUMF_WAVE_NB, 0, kArithPrePk>(a, mode, n_items, stream)
-                            : launch_wave_fc<CUMF_WAVE_NB, 0, kArithPre>(a, mode, n_items, stream);
-#endif
-  if (a.pre_words) return hipErrorInvalidValue;
-#if CUMF_WAVE_SPLITPK
-  if (mode != kModeMaterialize && splitpk_wanted(a)) return launch_wave_fc<CUMF_WAVE_NB, 0, kArithSplitPk>(a, mode, n_items, stream);
-#endif
-  return a.fast_words ? launch_wave_fc<CUMF_WAVE_NB, 0, kArithFast>(a, mode, n_items, stream)
-                      : launch_wave_fc<CUMF_WAVE_NB, 0, kArithSplit3>(a, mode, n_items, stream);
+  if (mode == kModeLU) return wave_lu_launch<CUMF_WAVE_NB>(a, r, whole, n_items, stream);  // part 1 of this file
+  return with_arith(r, [&](auto arith, auto fc) {
+    return launch_wave_fc<CUMF_WAVE_NB, decltype(fc)::value, decltype(arith)::value>(a, mode, n_items, stream);
+  });
 #endif
 }
 
