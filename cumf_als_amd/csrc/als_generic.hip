@@ -144,14 +144,12 @@ hipError_t launch_gram_generic(const KernelArgs& a, long n_items, hipStream_t st
   if (n_items <= 0) return hipSuccess;
   if (a.tt == nullptr || a.tt_half || a.tt_packed) return hipErrorInvalidValue;  // the fp32 f x f batch only
   const size_t lds = (size_t)kGenWindow * (a.f + 1) * sizeof(float);
-  hipLaunchKernelGGL(gram_generic_kernel, dim3((unsigned)n_items), dim3(kGenThreads), lds, stream, a);
-  return hipGetLastError();
+  return launch_kernel(gram_generic_kernel, dim3((unsigned)n_items), dim3(kGenThreads), lds, stream, a);
 }
 
 hipError_t launch_lu_global(float* A, const float* b, float* x, long batch, int f, hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
-  hipLaunchKernelGGL(lu_global_kernel, dim3((unsigned)batch), dim3(kGenThreads), (size_t)f * sizeof(float), stream, A, b, x, f);
-  return hipGetLastError();
+  return launch_kernel(lu_global_kernel, dim3((unsigned)batch), dim3(kGenThreads), (size_t)f * sizeof(float), stream, A, b, x, f);
 }
 
 }  // namespace cumf

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <type_traits>
 
 // Profiling build (make ablate -> libALS_ablate.so): the kernels additionally honour KernelArgs::dbg, switches that
 // make the results WRONG on purpose (no solve, no Gram pass, ...) to time parts of a kernel.  The production
@@ -30,6 +31,7 @@ enum { kModeCG = 0, kModeLU = 1, kModeMaterialize = 2, kModeLUExact = 3, kModeCG
 
 // Feature blocks of 16 including the slot that carries the rating value (RHS).
 __host__ __device__ constexpr int nb_for_f(int f) { return f / 16 + 1; }
+constexpr int kMaxNB = nb_for_f(kMaxF);  // 13
 // LDS system matrix G: f rows, column f = RHS.  CG reads rows with 16-byte loads (pitch a
 // multiple of 4 floats); the LU paths walk columns (odd pitch = conflict-free).
 __host__ __device__ constexpr int solve_ldg(int f, int mode) { return mode == kModeCG ? ((f + 1 + 3) & ~3) : (f + 1); }
@@ -224,16 +226,72 @@ __host__ __device__ constexpr unsigned presplit_pitch(int f) {
 hipError_t launch_presplit3(const float* src, void* dst, long long rows, int f, hipStream_t stream);
 hipError_t launch_pack_upper(const float* full, float* packed, long batch, int f, int unpack, hipStream_t stream);
 void set_last_error(int code);  // read (and cleared) by cumf_last_error
+// Timing pool, kernel names (als_launch.cpp)
 void set_kernel_timing(bool on);
 void note_item_kernel(const void* host_function);  // called by the launchers of the Gram(+solve) kernels
 const void* last_item_kernel();
 hipError_t last_kernel_ms(float* item_ms, float* reduce_ms);
 // sums over every timed launch sequence since the previous call (or since timing was switched on), then resets
 hipError_t kernel_ms_since_reset(float* item_ms, float* reduce_ms, int* launches);
+// NB-independent kernels (als_common.hip)
 hipError_t launch_quadratic_terms(const float* A, const float* b, const float* x, const float* reg, long batch, int f,
                                   double* out, hipStream_t stream);
 hipError_t launch_sse(const float* val, const int* row, const int* col, const float* thetaT, const float* XT,
                       long count, int f, int surpass_nan, double* out, hipStream_t stream);
+// CG with A streamed from global memory (f > 128); a_half: A stored as fp16
+hipError_t launch_cg_global(const float* A, const float* b, float* x, long batch, int f, int cg_iters, bool a_half,
+                            hipStream_t stream);
+
+// ---- Per-NB entry points: function templates of the kernel files, each explicitly instantiated in the translation unit
+// of its NB only (Makefile: als_kernels.hip once per CUMF_NB_SLICE, als_wave.hip once per CUMF_WAVE_NB and part).
+// als_kernels.hip, NB = 1 .. kMaxNB; slice_solve also NB = 0: the oracle-order LU of CUMF_ALS_LU_EXACT
+template <int NB>
+hipError_t slice_half_iteration(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream);
+template <int NB>
+hipError_t slice_solve(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,
+                       hipStream_t stream);
+template <int NB>
+hipError_t slice_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream);
+template <int NB>
+hipError_t slice_batched(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream);
+// als_wave.hip, NB = 2 .. kMaxNB; wave_lu_launch: NB <= kMaxWaveNB (part 1); wave_cg_hist: profiling build only
+// whole: every item of the launch is a whole row (the LU instance without the dump exit)
+template <int NB>
+hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream);
+template <int NB>
+hipError_t wave_solve_launch(const KernelArgs& a, int mode, long n_rows, hipStream_t stream);
+template <int NB>
+hipError_t wave_lu_launch(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream);
+template <int NB>
+hipError_t wave_cg_hist(unsigned long long* out16);
+
+// The one NB decoder: go(std::integral_constant<int, NB>{}) for LO <= nb <= HI, hipErrorInvalidValue otherwise.
+template <int LO, int HI, class Go>
+hipError_t with_nb(int nb, Go&& go) {
+  if constexpr (LO > HI)
+    return hipErrorInvalidValue;
+  else
+    return nb == LO ? go(std::integral_constant<int, LO>{}) : with_nb<LO + 1, HI>(nb, go);
+}
+
+// One launch: the dynamic-LDS opt-in above 64 KB, the launch, its error.  launch_item_kernel (NOTE): a Gram(+solve)
+// kernel, also recorded for cumf_last_kernel_name.
+template <bool NOTE = false, typename... P, typename... A>
+hipError_t launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  if (NOTE) note_item_kernel(fn);
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+  return hipGetLastError();
+}
+template <typename... P, typename... A>
+hipError_t launch_item_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                              const A&... args) {
+  return launch_kernel<true>(kernel, grid, block, lds, stream, args...);
+}
 
 }  // namespace cumf
 

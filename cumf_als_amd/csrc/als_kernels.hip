@@ -23,13 +23,8 @@
 //     same sequential FMA chain one reference thread computes (als.h:39-143).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 #include "als_internal.h"
 #include "als_device.h"
@@ -37,22 +32,12 @@
 
 namespace cumf {
 
-
-// The file is compiled once per NB (Makefile: -DCUMF_NB_SLICE=1..13, the kernels of that
-// feature-block count) plus once with -DCUMF_NB_SLICE=0 (dispatch, NB-independent kernels,
-// shared state), so that the build runs in parallel; without the macro everything lands in
-// one translation unit.
-#if !defined(CUMF_NB_SLICE)
-#define CUMF_SLICE_COMMON 1
-#define CUMF_SLICE_HAS(n) 1
-#elif CUMF_NB_SLICE == 0
-#define CUMF_SLICE_COMMON 1
-#define CUMF_SLICE_HAS(n) 0
-#else
-#define CUMF_SLICE_COMMON 0
-#define CUMF_SLICE_HAS(n) (CUMF_NB_SLICE == (n))
+// The file is compiled once per NB (Makefile: -DCUMF_NB_SLICE=1..13, the kernels of that feature-block count; 0: the
+// oracle-order LU alone), so that the build runs in parallel.  Each object instantiates the entry points of its NB only
+// (end of file).
+#ifndef CUMF_NB_SLICE
+#error "compile with -DCUMF_NB_SLICE=<feature blocks>"
 #endif
-
 
 // The accumulator LU pays off from f = 96 on (measured: f = 64 18.8 vs 18.0 ms, f = 10 0.67 vs 0.56 ms with
 // the thread-grid LU; f = 100 35.7 vs 36.8, f = 128 62.2 vs 63.8, f = 200 200 vs 224).
@@ -939,335 +924,9 @@ __global__ __launch_bounds__(kThreads) void solve_lds_kernel(const float* __rest
     cg_solve_lds<NB>(G, ldg, f, smem + solve_g_floats(f, MODE), x + sys * f, cg_iters, tid);
 }
 
-#if CUMF_SLICE_COMMON
-// CG with A streamed from global memory every mat-vec, for f too large for an
-// LDS-resident system (f > 128).  One workgroup per system, thread t owns row t
-// (blockDim = f rounded up to 64; same shape as cg.cu:36-231, wave64 reductions).
-__global__ void cg_global_kernel(const float* __restrict__ A, float* __restrict__ x, const float* __restrict__ b,
-                                 int f, int cg_iters, int a_half) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-  float* ps = smem;             // f
-  float* red = smem + blockDim.x;  // nwaves
-  const float* As = A + (size_t)blockIdx.x * f * f;
-  const _Float16* Ah = reinterpret_cast<const _Float16*>(A) + (size_t)blockIdx.x * f * f;  // a_half (cg.cu:253,289)
-  float* xs = x + (size_t)blockIdx.x * f;
-  const bool own = tid < f;
-
-  auto block_sum = [&](float v) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < nwaves; ++w) s += red[w];
-    return s;
-  };
-  auto matvec = [&]() {
-    float s = 0.f;
-    if (own) {
-      if (a_half)
-        for (int j = 0; j < f; ++j) s = fmaf((float)Ah[(size_t)j * f + tid], ps[j], s);
-      else
-        for (int j = 0; j < f; ++j) s = fmaf(As[(size_t)j * f + tid], ps[j], s);
-    }
-    return s;
-  };
-
-  float xv = own ? xs[tid] : 0.f;
-  if (own) ps[tid] = xv;
-  __syncthreads();
-  float r = own ? (b[(size_t)blockIdx.x * f + tid] - matvec()) : 0.f;
-  __syncthreads();
-  float p = r;
-  if (own) ps[tid] = p;
-  float rsold = block_sum(r * r);  // its barriers also publish ps
-  for (int iter = 0; iter < cg_iters; ++iter) {
-    const float ap = matvec();
-    const float pap = block_sum(own ? p * ap : 0.f);
-    const float alpha = rsold / pap;
-    xv = fmaf(alpha, p, xv);
-    r = fmaf(-alpha, ap, r);
-    const float rsnew = block_sum(own ? r * r : 0.f);
-    if ((double)rsnew < 1e-4) break;
-    const float beta = rsnew / rsold;
-    rsold = rsnew;
-    p = fmaf(beta, p, r);
-    __syncthreads();
-    if (own) ps[tid] = p;
-    __syncthreads();
-  }
-  if (own) xs[tid] = xv;
-}
-
 // ----------------------------------------------------------------------------------
-// Sum of squared errors (RMSE kernel + Sasum, als.cu:191-219, 979-991): 16 lanes per
-// rating, 8/16-byte gathers of both factor rows, fp64 accumulation across ratings.
+// Launchers: the per-NB entry points (als_internal.h), called through with_nb by als_launch.cpp
 // ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void sse_kernel(const float* __restrict__ val, const int* __restrict__ row,
-                                                       const int* __restrict__ col, const float* __restrict__ thetaT,
-                                                       const float* __restrict__ XT, long long count, int f,
-                                                       int surpass_nan, double* __restrict__ out) {
-  __shared__ double red[kThreads / 64];
-  const int tid = threadIdx.x, sub = tid & 15;
-  const long long per_block = kThreads / 16;
-  double local = 0.0;
-  for (long long base = (long long)blockIdx.x * per_block; base < count; base += (long long)gridDim.x * per_block) {
-    const long long i = base + (tid >> 4);
-    float e = 0.f;
-    if (i < count) {
-      const float* th = thetaT + (size_t)col[i] * f;
-      const float* xr = XT + (size_t)row[i] * f;
-      float s = 0.f;
-      int first_nan = f;
-      if (surpass_nan) {  // SURPASS_NAN (als.cu:201-211): stop at the first NaN factor entry
-        for (int k = sub * 2; k < f; k += 32) {
-          const f32x2 a = *reinterpret_cast<const f32x2*>(th + k);
-          const f32x2 b = *reinterpret_cast<const f32x2*>(xr + k);
-          if ((a[0] != a[0] || b[0] != b[0]) && k < first_nan) first_nan = k;
-          if ((a[1] != a[1] || b[1] != b[1]) && k + 1 < first_nan) first_nan = k + 1;
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-          const int other = __shfl_xor(first_nan, o);
-          first_nan = other < first_nan ? other : first_nan;
-        }
-      }
-      for (int k = sub * 2; k < f; k += 32) {
-        const f32x2 a = *reinterpret_cast<const f32x2*>(th + k);
-        const f32x2 b = *reinterpret_cast<const f32x2*>(xr + k);
-        if (k < first_nan) s = fmaf(a[0], b[0], s);
-        if (k + 1 < first_nan) s = fmaf(a[1], b[1], s);
-      }
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
-      e = val[i] - s;
-    }
-    if (sub == 0 && i < count) local += (double)e * (double)e;
-  }
-  // block reduction in fp64
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-  if ((tid & 63) == 0) red[tid >> 6] = local;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0;
-    for (int w = 0; w < kThreads / 64; ++w) s += red[w];
-    atomicAdd(out, s);
-  }
-}
-
-// ----------------------------------------------------------------------------------
-// Packed upper triangle of a batch of symmetric f x f Grams (row i keeps columns i .. f-1,
-// f (f + 1) / 2 floats per system): the payload of the multi-GPU partial-Gram reduction
-// (hugewiki.cu:2703-2717 moves the full f x f per GPU; half of it is redundant).
-// ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void pack_upper_kernel(const float* __restrict__ full, float* __restrict__ packed,
-                                                              int f) {
-  const size_t sys = blockIdx.x;
-  const float* A = full + sys * (size_t)f * f;
-  float* P = packed + sys * (size_t)(f * (f + 1) / 2);
-  for (int e = threadIdx.x; e < f * f; e += kThreads) {
-    const int i = e / f, j = e - i * f;
-    if (j >= i) P[i * f - i * (i - 1) / 2 + (j - i)] = A[e];
-  }
-}
-__global__ __launch_bounds__(kThreads) void unpack_upper_kernel(const float* __restrict__ packed, float* __restrict__ full,
-                                                                int f) {
-  const size_t sys = blockIdx.x;
-  float* A = full + sys * (size_t)f * f;
-  const float* P = packed + sys * (size_t)(f * (f + 1) / 2);
-  for (int e = threadIdx.x; e < f * f; e += kThreads) {
-    const int i = e / f, j = e - i * f;
-    const int a = i < j ? i : j, b = i < j ? j : i;
-    A[e] = P[a * f - a * (a - 1) / 2 + (b - a)];
-  }
-}
-// ----------------------------------------------------------------------------------
-// Train SSE from materialised systems (round 4; the multi-GPU `reduce` scheme, where the Gram batch is reduced across
-// ranks and solved by a batched solver): sum_u (r - x_u . t)^2 = sum r^2 - (2 t.b - t^T G t) with G = A - reg I.  One
-// workgroup per system adds 2 t.b - t^T A t + reg |t|^2 (fp64) to *out; sum r^2 is a constant of the data.  A is read by
-// columns (symmetric: y_j = sum_i A[i][j] t_i, coalesced over j).  Systems with reg < 0 (the caller's mark for "no rating": its solution is NaN) are skipped;
-// reg == 0 is a valid system (lambda = 0).
-// ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void quadratic_terms_kernel(const float* __restrict__ A, const float* __restrict__ b,
-                                                                   const float* __restrict__ x, const float* __restrict__ reg,
-                                                                   int f, double* __restrict__ out) {
-  __shared__ float xs[256];
-  __shared__ double red[kThreads / 64];
-  const size_t sys = blockIdx.x;
-  const float rg = reg[sys];
-  if (!(rg >= 0.f)) return;  // uniform: negative (or NaN) = no rating
-  const int tid = threadIdx.x;
-  if (tid < f) xs[tid] = x[sys * f + tid];
-  __syncthreads();
-  double t = 0.0;
-  if (tid < f) {
-    const float* col = A + sys * (size_t)f * f + tid;
-    float y = 0.f;
-    for (int i = 0; i < f; ++i) y = fmaf(col[(size_t)i * f], xs[i], y);
-    const float xj = xs[tid];
-    t = (double)xj * (2.0 * (double)b[sys * f + tid] - (double)y + (double)rg * (double)xj);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-  if ((tid & 63) == 0) red[tid >> 6] = t;
-  __syncthreads();
-  if (tid == 0) {
-    double sum = 0.0;
-    for (int w = 0; w < kThreads / 64; ++w) sum += red[w];
-    atomicAdd(out, sum);
-  }
-}
-
-// Gram mode "fast": factor table -> (h, l) f16 words of 4096 x (round to nearest even; als_wave.hip
-// kArithFast).  Values whose scaled magnitude leaves the f16 range (|x| >= 15.99, +-inf included) are reported
-// through *flag (bit 0); NaN entries (rows without ratings) are not.
-__global__ __launch_bounds__(256) void presplit_f16x2_kernel(const float* __restrict__ src,
-                                                            unsigned* __restrict__ dst, size_t n4, size_t n,
-                                                            int* __restrict__ flag) {
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-  auto word = [](float x, bool& bad) {
-    const float s = x * 4096.0f;
-    // NaN is NOT a range violation: rows / columns without ratings carry NaN factors by design (0/0 in CG, a
-    // zero pivot in LU: cg.cu:128) and are never gathered; a NaN that IS gathered shows up in the Gram
-    // kernel's own probe (bit 1).  +-inf and finite values beyond the f16 range are flagged.
-    bad = bad || (__builtin_fabsf(s) >= 65504.0f);
-    const _Float16 h = (_Float16)s;
-    const _Float16 l = (_Float16)(s - (float)h);
-    h2 w = {h, l};
-    return __builtin_bit_cast(unsigned, w);
-  };
-  bool bad = false;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    u4 o = {word(v[0], bad), word(v[1], bad), word(v[2], bad), word(v[3], bad)};
-    reinterpret_cast<u4*>(dst)[i] = o;
-  }
-  for (size_t i = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = word(src[i], bad);
-  if (bad) atomicOr(flag, 1);
-}
-hipError_t launch_presplit(const float* src, unsigned* dst, size_t n, int* flag, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  const bool aligned = (reinterpret_cast<uintptr_t>(src) % 16 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
-  const size_t n4 = aligned ? n / 4 : 0;
-  size_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(presplit_f16x2_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, dst, n4, n, flag);
-  return hipGetLastError();
-}
-
-hipError_t launch_pack_upper(const float* full, float* packed, long batch, int f, int unpack, hipStream_t stream) {
-  if (batch <= 0) return hipSuccess;
-  if (unpack)
-    hipLaunchKernelGGL(unpack_upper_kernel, dim3((unsigned)batch), dim3(kThreads), 0, stream, full, packed, f);
-  else
-    hipLaunchKernelGGL(pack_upper_kernel, dim3((unsigned)batch), dim3(kThreads), 0, stream, full, packed, f);
-  return hipGetLastError();
-}
-
-hipError_t launch_quadratic_terms(const float* A, const float* b, const float* x, const float* reg, long batch, int f,
-                                  double* out, hipStream_t stream) {
-  if (batch <= 0) return hipSuccess;
-  if (f > 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(quadratic_terms_kernel, dim3((unsigned)batch), dim3(kThreads), 0, stream, A, b, x, reg, f, out);
-  return hipGetLastError();
-}
-
-// ----------------------------------------------------------------------------------
-// Launchers
-// ----------------------------------------------------------------------------------
-
-// Optional per-kernel HIP-event timing of the last half-iteration (bench.py's roofline
-// leg): events are recorded on the SAME stream the kernels are launched on.
-#endif  // CUMF_SLICE_COMMON
-
-#if CUMF_SLICE_COMMON
-bool g_timing = false;
-hipEvent_t g_ev[3] = {nullptr, nullptr, nullptr};
-bool g_timed_item = false, g_timed_reduce = false;
-#else
-extern bool g_timing;
-extern hipEvent_t g_ev[3];
-extern bool g_timed_item, g_timed_reduce;
-#endif
-// Every timed launch sequence starts with timing_begin(): it takes the next event triple of a pool (so that the
-// launches of a half-iteration made of several -- X_BATCH / THETA_BATCH plans, the pipeline pieces of the multi-GPU
-// gather scheme -- can be summed afterwards, kernel_ms_since_reset) and leaves it in g_ev.
-void timing_begin();
-
-#if CUMF_SLICE_COMMON
-// the Gram(+solve) kernel the last half-iteration dispatched (bench.py reads its name for roofline.kernel)
-static std::atomic<const void*> g_last_item_kernel{nullptr};
-void note_item_kernel(const void* host_function) { g_last_item_kernel.store(host_function, std::memory_order_relaxed); }
-const void* last_item_kernel() { return g_last_item_kernel.load(std::memory_order_relaxed); }
-namespace {
-struct TimedLaunch {
-  hipEvent_t ev[3];
-  bool item, reduce;
-};
-constexpr size_t kTimedPool = 1024;
-std::vector<TimedLaunch> g_timed;  // pool of event triples, created on first use
-size_t g_timed_used = 0;           // launches since the last reset (the newest one is g_timed[g_timed_used - 1])
-std::mutex g_timed_mutex;
-}  // namespace
-void set_kernel_timing(bool on) {
-  std::lock_guard<std::mutex> lock(g_timed_mutex);
-  g_timing = on;
-  if (on && g_timed.empty()) {
-    g_timed.resize(kTimedPool);
-    for (auto& t : g_timed) {
-      for (auto& e : t.ev) (void)hipEventCreate(&e);
-      t.item = t.reduce = false;
-    }
-  }
-}
-void timing_begin() {
-  if (!g_timing) return;
-  std::lock_guard<std::mutex> lock(g_timed_mutex);
-  if (g_timed_used > 0) {  // the flags of the previous launch are final now
-    g_timed[g_timed_used - 1].item = g_timed_item;
-    g_timed[g_timed_used - 1].reduce = g_timed_reduce;
-  }
-  if (g_timed_used == kTimedPool) g_timed_used = 0;  // nobody read for 1024 launches: start over
-  TimedLaunch& t = g_timed[g_timed_used++];
-  for (int i = 0; i < 3; ++i) g_ev[i] = t.ev[i];
-}
-hipError_t last_kernel_ms(float* item_ms, float* reduce_ms) {
-  *item_ms = 0.f;
-  *reduce_ms = 0.f;
-  if (!g_ev[0]) return hipSuccess;
-  hipError_t e = hipEventSynchronize(g_ev[2]);
-  if (e != hipSuccess) return e;
-  if (g_timed_item) (void)hipEventElapsedTime(item_ms, g_ev[0], g_ev[1]);
-  if (g_timed_reduce) (void)hipEventElapsedTime(reduce_ms, g_ev[1], g_ev[2]);
-  return hipSuccess;
-}
-hipError_t kernel_ms_since_reset(float* item_ms, float* reduce_ms, int* launches) {
-  std::lock_guard<std::mutex> lock(g_timed_mutex);
-  *item_ms = 0.f;
-  *reduce_ms = 0.f;
-  *launches = (int)g_timed_used;
-  if (g_timed_used > 0) {
-    g_timed[g_timed_used - 1].item = g_timed_item;
-    g_timed[g_timed_used - 1].reduce = g_timed_reduce;
-  }
-  for (size_t i = 0; i < g_timed_used; ++i) {
-    TimedLaunch& t = g_timed[i];
-    hipError_t e = hipEventSynchronize(t.ev[2]);
-    if (e != hipSuccess) return e;
-    float ms = 0.f;
-    if (t.item && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) *item_ms += ms;
-    if (t.reduce && hipEventElapsedTime(&ms, t.ev[1], t.ev[2]) == hipSuccess) *reduce_ms += ms;
-  }
-  g_timed_used = 0;
-  return hipSuccess;
-}
-#endif  // CUMF_SLICE_COMMON
-
 template <int NB, typename VT, int MODE>
 static hipError_t launch_nb(const KernelArgs& a, long n_items, long n_mrows, hipStream_t stream) {
   const size_t stage_floats = (2 * (size_t)kStage + 8) * Geo<NB>::LD;  // + read-ahead pad of mma_stage
@@ -1277,32 +936,20 @@ static hipError_t launch_nb(const KernelArgs& a, long n_items, long n_mrows, hip
     floats = floats > solve ? floats : solve;
   }
   const size_t lds = floats * sizeof(float);
-  hipError_t e;
-  if (lds > 64 * 1024) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(als_item_kernel<NB, VT, MODE>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(als_reduce_kernel<NB, MODE>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
   if (n_items > 0) {
-    note_item_kernel(reinterpret_cast<const void*>(als_item_kernel<NB, VT, MODE>));
-    hipLaunchKernelGGL((als_item_kernel<NB, VT, MODE>), dim3((unsigned)n_items), dim3(kThreads), lds, stream, a);
-    e = hipGetLastError();
+    hipError_t e = launch_item_kernel(als_item_kernel<NB, VT, MODE>, dim3((unsigned)n_items), dim3(kThreads), lds, stream, a);
     if (e != hipSuccess) return e;
   }
   if (n_mrows > 0) {
     const size_t lds2 = (MODE == kModeMaterialize) ? 0 : lds;
-    hipLaunchKernelGGL((als_reduce_kernel<NB, MODE>), dim3((unsigned)n_mrows), dim3(kThreads), lds2, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    return launch_kernel(als_reduce_kernel<NB, MODE>, dim3((unsigned)n_mrows), dim3(kThreads), lds2, stream, a);
   }
   return hipSuccess;
 }
 
+// the workgroup kernels: the items (als_item_kernel), then the chunked rows (als_reduce_kernel)
 template <int NB>
-static hipError_t launch_mode(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream) {
+hipError_t slice_half_iteration(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream) {
   const bool v4 = (a.f % 4 == 0);
   if (mode == kModeMaterialize)
     return v4 ? launch_nb<NB, f32x4, kModeMaterialize>(a, n_items, n_mrows, stream)
@@ -1326,67 +973,44 @@ static hipError_t launch_solve_nb(const float* A, const float* b, float* x, long
                                 : (MODE == kModeLU ? lu_lds_floats(NB, f) : solve_lds_floats(f, MODE));
   const size_t lds = floats * sizeof(float);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(solve_lds_kernel<NB, MODE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((solve_lds_kernel<NB, MODE>), dim3((unsigned)batch), dim3(kThreads), lds, stream, A, b, x, f,
-                     cg_iters, a_half);
-  return hipGetLastError();
+  return launch_kernel(solve_lds_kernel<NB, MODE>, dim3((unsigned)batch), dim3(kThreads), lds, stream, A, b, x, f,
+                       cg_iters, a_half);
 }
 
-// wave-per-item kernels (als_wave.hip), one translation unit per NB
-// whole: every item of the launch is a whole row (the LU instance without the dump exit)
+// batched solve of materialised systems: LDS-resident CG (f <= 128) or register-resident LU (f <= 200); NB = 0: the
+// oracle-order LU (kModeLUExact)
 template <int NB>
-hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream);
-template <int NB>
-hipError_t wave_solve_launch(const KernelArgs& a, int mode, long n_rows, hipStream_t stream);
-#define CUMF_DECLARE_WAVE(N)                                                                                                \
-  template <>                                                                                                               \
-  hipError_t wave_item_launch<N>(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream); \
-  template <>                                                                                                               \
-  hipError_t wave_solve_launch<N>(const KernelArgs& a, int mode, long n_rows, hipStream_t stream);
-CUMF_DECLARE_WAVE(2) CUMF_DECLARE_WAVE(3) CUMF_DECLARE_WAVE(4) CUMF_DECLARE_WAVE(5)
-CUMF_DECLARE_WAVE(6) CUMF_DECLARE_WAVE(7) CUMF_DECLARE_WAVE(8) CUMF_DECLARE_WAVE(9) CUMF_DECLARE_WAVE(10)
-CUMF_DECLARE_WAVE(11) CUMF_DECLARE_WAVE(12) CUMF_DECLARE_WAVE(13)
+hipError_t slice_solve(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,
+                       hipStream_t stream) {
+  if (mode == kModeCG || mode == kModeCGHalf) {
+    if constexpr (NB != 0 && NB <= kMaxFusedNB)
+      return launch_solve_nb<NB, kModeCG>(A, b, x, batch, f, cg_iters, stream, mode == kModeCGHalf);
+    return hipErrorInvalidValue;
+  }
+  return launch_solve_nb<NB, kModeLU>(A, b, x, batch, f, cg_iters, stream);
+}
 
 // solver of the chunked rows on its own (the items came from the wave kernels): Route::chunked
 template <int NB>
-static hipError_t launch_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream) {
+hipError_t slice_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream) {
   if (n_mrows <= 0) return hipSuccess;
   if constexpr (NB >= 2) {
     if (r.chunked == kSolveWaveCG) return wave_solve_launch<NB>(a, mode, n_mrows, stream);
   }
-  if (mode == kModeMaterialize) {
-    hipLaunchKernelGGL((als_reduce_kernel<NB, kModeMaterialize>), dim3((unsigned)n_mrows), dim3(kThreads), 0, stream, a);
-  } else if (mode == kModeCG) {
+  const dim3 grid((unsigned)n_mrows), block(kThreads);
+  if (mode == kModeMaterialize) return launch_kernel(als_reduce_kernel<NB, kModeMaterialize>, grid, block, 0, stream, a);
+  if (mode == kModeCG) {
     if constexpr (NB <= kMaxFusedNB) {
       if (a.f > kVecLd) return hipErrorInvalidValue;
       const size_t lds = solve_lds_floats(a.f, kModeCG) * sizeof(float);
-      if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(als_reduce_kernel<NB, kModeCG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL((als_reduce_kernel<NB, kModeCG>), dim3((unsigned)n_mrows), dim3(kThreads), lds, stream, a);
+      return launch_kernel(als_reduce_kernel<NB, kModeCG>, grid, block, lds, stream, a);
     } else {
       return hipErrorInvalidValue;
     }
-  } else {
-    const size_t lds = lu_fused_lds_floats<NB>(a.f) * sizeof(float);
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(als_reduce_kernel<NB, kModeLU>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((als_reduce_kernel<NB, kModeLU>), dim3((unsigned)n_mrows), dim3(kThreads), lds, stream, a);
   }
-  return hipGetLastError();
+  const size_t lds = lu_fused_lds_floats<NB>(a.f) * sizeof(float);
+  return launch_kernel(als_reduce_kernel<NB, kModeLU>, grid, block, lds, stream, a);
 }
-template <int NB>
-hipError_t slice_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream);
-
 
 // Large systems (f >= 112): the Gram of every row is dumped as accumulator tiles (two waves per item,
 // als_wave_multi_kernel) and a solver kernel (single-wave LU up to NB = 10, the 4-wave lu_solve_mfma
@@ -1394,7 +1018,7 @@ hipError_t slice_reduce_only(const KernelArgs& a, int mode, const Route& r, long
 // in device memory, separate solver", als.cu:782-831), with tiles instead of full f x f matrices and
 // in batches of the pooled tile buffer (als_plan.cpp: up to 48 GiB, usually ONE batch).
 template <int NB>
-static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
+hipError_t slice_batched(const KernelArgs& a0, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
   if constexpr (NB < 2) {
     return hipErrorInvalidValue;
   } else {
@@ -1409,7 +1033,7 @@ static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const Route&
     a.item_rowlen = L.c_rowlen;
     e = wave_item_launch<NB>(a, kModeLU, r, false, L.n_citems, stream);  // every item has a slot: nothing is solved in place
     if (e != hipSuccess) return e;
-    e = launch_reduce_only<NB>(a0, mode, r, L.n_mrows, stream);
+    e = slice_reduce_only<NB>(a0, mode, r, L.n_mrows, stream);
     if (e != hipSuccess) return e;
   }
   // 2. whole rows: solved by the two waves that formed the Gram, in one launch, or through the tile buffer
@@ -1439,219 +1063,22 @@ static hipError_t launch_batched_nb(const KernelArgs& a0, int mode, const Route&
     a.mrow_rowlen = L.w_rowlen + w0;
     e = wave_item_launch<NB>(a, kModeLU, r, false, cnt, stream);
     if (e != hipSuccess) return e;
-    e = launch_reduce_only<NB>(a, mode, r, cnt, stream);
+    e = slice_reduce_only<NB>(a, mode, r, cnt, stream);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
   }
 }
-template <int NB>
-hipError_t slice_batched(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream);
 
-// Per-NB entry points (one translation unit each, see CUMF_NB_SLICE above).
-template <int NB>
-hipError_t slice_half_iteration(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream);
-template <int NB>
-hipError_t slice_solve(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,
-                       hipStream_t stream);
-
-#define CUMF_DECLARE_SLICE(N)                                                                                   \
-  template <>                                                                                                    \
-  hipError_t slice_half_iteration<N>(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream); \
-  template <>                                                                                                    \
-  hipError_t slice_solve<N>(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters, \
-                            hipStream_t stream);                                                                 \
-  template <>                                                                                                    \
-  hipError_t slice_reduce_only<N>(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream); \
-  template <>                                                                                                    \
-  hipError_t slice_batched<N>(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream);
-#define CUMF_DEFINE_SLICE(N)                                                                                     \
-  template <>                                                                                                    \
-  hipError_t slice_half_iteration<N>(const KernelArgs& a, int mode, long n_items, long n_mrows,                 \
-                                     hipStream_t stream) {                                                       \
-    return launch_mode<N>(a, mode, n_items, n_mrows, stream);                                                    \
-  }                                                                                                              \
-  template <>                                                                                                    \
-  hipError_t slice_solve<N>(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters, \
-                            hipStream_t stream) {                                                                \
-    if (mode == kModeCG || mode == kModeCGHalf) {                                                                \
-      if constexpr (N <= kMaxFusedNB)                                                                            \
-        return launch_solve_nb<N, kModeCG>(A, b, x, batch, f, cg_iters, stream, mode == kModeCGHalf);            \
-      return hipErrorInvalidValue;                                                                               \
-    }                                                                                                            \
-    return launch_solve_nb<N, kModeLU>(A, b, x, batch, f, cg_iters, stream);                                     \
-  }                                                                                                              \
-  template <>                                                                                                    \
-  hipError_t slice_reduce_only<N>(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream) { \
-    return launch_reduce_only<N>(a, mode, r, n_mrows, stream);                                                   \
-  }                                                                                                              \
-  template <>                                                                                                    \
-  hipError_t slice_batched<N>(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) { \
-    return launch_batched_nb<N>(a, mode, r, L, stream);                                                          \
-  }
-
-CUMF_DECLARE_SLICE(1) CUMF_DECLARE_SLICE(2) CUMF_DECLARE_SLICE(3) CUMF_DECLARE_SLICE(4) CUMF_DECLARE_SLICE(5)
-CUMF_DECLARE_SLICE(6) CUMF_DECLARE_SLICE(7) CUMF_DECLARE_SLICE(8) CUMF_DECLARE_SLICE(9) CUMF_DECLARE_SLICE(10)
-CUMF_DECLARE_SLICE(11) CUMF_DECLARE_SLICE(12) CUMF_DECLARE_SLICE(13)
-#if CUMF_SLICE_HAS(1)
-CUMF_DEFINE_SLICE(1)
+// The entry points of this translation unit's NB (Makefile: one object per CUMF_NB_SLICE).  Slice 0 is only the
+// oracle-order LU (solve_lds_kernel<0, kModeLU>, CUMF_ALS_LU_EXACT); the NB-independent kernels are in als_common.hip.
+#if CUMF_NB_SLICE == 0
+template hipError_t slice_solve<0>(const float*, const float*, float*, long, int, int, int, hipStream_t);
+#else
+template hipError_t slice_half_iteration<CUMF_NB_SLICE>(const KernelArgs&, int, long, long, hipStream_t);
+template hipError_t slice_solve<CUMF_NB_SLICE>(const float*, const float*, float*, long, int, int, int, hipStream_t);
+template hipError_t slice_reduce_only<CUMF_NB_SLICE>(const KernelArgs&, int, const Route&, long, hipStream_t);
+template hipError_t slice_batched<CUMF_NB_SLICE>(const KernelArgs&, int, const Route&, const PlanLists&, hipStream_t);
 #endif
-#if CUMF_SLICE_HAS(2)
-CUMF_DEFINE_SLICE(2)
-#endif
-#if CUMF_SLICE_HAS(3)
-CUMF_DEFINE_SLICE(3)
-#endif
-#if CUMF_SLICE_HAS(4)
-CUMF_DEFINE_SLICE(4)
-#endif
-#if CUMF_SLICE_HAS(5)
-CUMF_DEFINE_SLICE(5)
-#endif
-#if CUMF_SLICE_HAS(6)
-CUMF_DEFINE_SLICE(6)
-#endif
-#if CUMF_SLICE_HAS(7)
-CUMF_DEFINE_SLICE(7)
-#endif
-#if CUMF_SLICE_HAS(8)
-CUMF_DEFINE_SLICE(8)
-#endif
-#if CUMF_SLICE_HAS(9)
-CUMF_DEFINE_SLICE(9)
-#endif
-#if CUMF_SLICE_HAS(10)
-CUMF_DEFINE_SLICE(10)
-#endif
-#if CUMF_SLICE_HAS(11)
-CUMF_DEFINE_SLICE(11)
-#endif
-#if CUMF_SLICE_HAS(12)
-CUMF_DEFINE_SLICE(12)
-#endif
-#if CUMF_SLICE_HAS(13)
-CUMF_DEFINE_SLICE(13)
-#endif
-
-#if CUMF_SLICE_COMMON
-#define CUMF_NB_CASE(N, call) case N: return call;
-
-// the wave kernels of one launch, by NB (als_wave.hip)
-static hipError_t wave_items(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream) {
-  switch (nb_for_f(a.f)) {
-#define CUMF_WAVE(N) CUMF_NB_CASE(N, wave_item_launch<N>(a, mode, r, whole, n_items, stream))
-    CUMF_WAVE(2) CUMF_WAVE(3) CUMF_WAVE(4) CUMF_WAVE(5) CUMF_WAVE(6) CUMF_WAVE(7)
-#undef CUMF_WAVE
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// One-wave path: the items of the plan (Route::n_short, Route::chunk_first), then launch_half_iteration's reduce phase
-static hipError_t one_wave_items(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
-  KernelArgs aw = a;
-  long n_items = L.n_items;
-  if (r.chunk_first) {
-    aw.item_row = L.w_row, aw.item_begin = L.w_begin, aw.item_len = L.w_len;
-    aw.item_slot = nullptr, aw.item_rowlen = L.w_rowlen;
-    n_items = L.n_witems;
-  }
-  if (r.n_short > 0) {  // the last items; first: the tail of the long items then fills in behind it
-    n_items -= r.n_short;
-    KernelArgs as = aw;
-    as.item_row += n_items, as.item_begin += n_items, as.item_len += n_items, as.item_rowlen += n_items;
-    hipError_t e = launch_short_cg(as, r.n_short, stream);
-    if (e != hipSuccess) return e;
-  }
-  if (r.chunk_first) {
-    KernelArgs ac = a;
-    ac.item_row = L.c_row, ac.item_begin = L.c_begin, ac.item_len = L.c_len;
-    ac.item_slot = L.c_slot, ac.item_rowlen = L.c_rowlen;
-    hipError_t e = wave_items(ac, mode, r, false, L.n_citems, stream);
-    if (e != hipSuccess) return e;
-  }
-  return wave_items(aw, mode, r, r.chunk_first || L.n_mrows == 0, n_items, stream);
-}
-
-hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
-  const int nb = nb_for_f(a.f);
-  // item phase (event 0 -> 1), then the chunked rows' solver (1 -> 2); the two-wave path interleaves them (item phase only)
-  timing_begin();
-  if (g_timing) (void)hipEventRecord(g_ev[0], stream);
-  g_timed_item = r.path == kPathTwoWave || L.n_items > 0;
-  g_timed_reduce = r.path != kPathTwoWave && L.n_mrows > 0;
-  hipError_t e = hipErrorInvalidValue;
-  bool reduce_done = false;
-  switch (r.path) {
-    case kPathTwoWave:
-      switch (nb) {
-#define CUMF_BATCHED(N) case N: e = slice_batched<N>(a, mode, r, L, stream); break;
-        CUMF_BATCHED(8) CUMF_BATCHED(9) CUMF_BATCHED(10) CUMF_BATCHED(11) CUMF_BATCHED(12) CUMF_BATCHED(13)
-#undef CUMF_BATCHED
-      }
-      reduce_done = true;
-      break;
-    case kPathOneWave: e = one_wave_items(a, mode, r, L, stream); break;
-    case kPathWorkgroup:
-      switch (nb) {
-#define CUMF_HALF(N) case N: e = slice_half_iteration<N>(a, mode, L.n_items, 0, stream); break;
-        CUMF_HALF(1) CUMF_HALF(2) CUMF_HALF(3) CUMF_HALF(4) CUMF_HALF(5) CUMF_HALF(6) CUMF_HALF(7)
-        CUMF_HALF(8) CUMF_HALF(9) CUMF_HALF(10) CUMF_HALF(11) CUMF_HALF(12) CUMF_HALF(13)
-#undef CUMF_HALF
-      }
-      break;
-    default: break;
-  }
-  if (g_timing) (void)hipEventRecord(g_ev[1], stream);
-  if (e == hipSuccess && !reduce_done && L.n_mrows > 0) {
-    switch (nb) {
-#define CUMF_REDUCE(N)                                                                                    \
-  case N:                                                                                                 \
-    e = r.path == kPathOneWave ? slice_reduce_only<N>(a, mode, r, L.n_mrows, stream)                      \
-                               : slice_half_iteration<N>(a, mode, 0, L.n_mrows, stream);                  \
-    break;
-      CUMF_REDUCE(1) CUMF_REDUCE(2) CUMF_REDUCE(3) CUMF_REDUCE(4) CUMF_REDUCE(5) CUMF_REDUCE(6) CUMF_REDUCE(7)
-      CUMF_REDUCE(8) CUMF_REDUCE(9) CUMF_REDUCE(10) CUMF_REDUCE(11) CUMF_REDUCE(12) CUMF_REDUCE(13)
-#undef CUMF_REDUCE
-      default: e = hipErrorInvalidValue;
-    }
-  }
-  if (g_timing) (void)hipEventRecord(g_ev[2], stream);
-  return e;
-}
-
-hipError_t launch_solve_batched(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,
-                                hipStream_t stream) {
-  if (batch <= 0) return hipSuccess;
-  if (mode == kModeLUExact) return launch_solve_nb<0, kModeLU>(A, b, x, batch, f, 0, stream);
-  if (f > 128 && (mode == kModeCG || mode == kModeCGHalf)) {  // system too large for the LDS: A streamed from global memory
-    const int threads = ((f + 63) / 64) * 64;
-    const size_t lds = (threads + 16) * sizeof(float);
-    hipLaunchKernelGGL(cg_global_kernel, dim3((unsigned)batch), dim3(threads), lds, stream, A, x, b, f, cg_iters,
-                       (int)(mode == kModeCGHalf));
-    return hipGetLastError();
-  }
-  // LDS-resident CG (f <= 128) or register-resident LU (f <= 200)
-#define CUMF_SOLVE(N) CUMF_NB_CASE(N, slice_solve<N>(A, b, x, batch, f, mode, cg_iters, stream))
-  switch (nb_for_f(f)) {
-    CUMF_SOLVE(1) CUMF_SOLVE(2) CUMF_SOLVE(3) CUMF_SOLVE(4) CUMF_SOLVE(5) CUMF_SOLVE(6) CUMF_SOLVE(7)
-    CUMF_SOLVE(8) CUMF_SOLVE(9) CUMF_SOLVE(10) CUMF_SOLVE(11) CUMF_SOLVE(12) CUMF_SOLVE(13)
-    default: return hipErrorInvalidValue;
-  }
-#undef CUMF_SOLVE
-}
-
-hipError_t launch_sse(const float* val, const int* row, const int* col, const float* thetaT, const float* XT,
-                      long count, int f, int surpass_nan, double* out, hipStream_t stream) {
-  hipError_t e = hipMemsetAsync(out, 0, sizeof(double), stream);
-  if (e != hipSuccess) return e;
-  if (count <= 0) return hipSuccess;
-  long blocks = (count + 15) / 16;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(sse_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, val, row, col, thetaT, XT,
-                     (long long)count, f, surpass_nan, out);
-  return hipGetLastError();
-}
-
-#endif  // CUMF_SLICE_COMMON
 
 }  // namespace cumf

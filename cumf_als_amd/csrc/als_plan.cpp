@@ -794,10 +794,6 @@ extern "C" int cumf_set_debug_switches(int switches) {
 }
 // switch 65536: rows by the number of CG iterations they ran (bins 0 .. 15), read and cleared; f selects the kernels'
 // feature-block count (the profiling build has NB = 5, 7, 13)
-namespace cumf {
-template <int NB>
-hipError_t wave_cg_hist(unsigned long long* out16);
-}
 extern "C" int cumf_debug_cg_histogram(int f, unsigned long long* out16) {
   if (!out16) return (int)hipErrorInvalidValue;
   CUMF_HIP_CHECK(hipDeviceSynchronize());

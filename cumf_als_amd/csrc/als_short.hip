@@ -190,11 +190,8 @@ bool short_cg_available(int f) { return f >= 32 && f <= 128; }
 hipError_t launch_short_cg(const KernelArgs& a, long n_items, hipStream_t stream) {
   if (n_items <= 0) return hipSuccess;
   if (!short_cg_available(a.f)) return hipErrorInvalidValue;
-  if (a.f > 64)
-    hipLaunchKernelGGL((als_short_cg_kernel<true>), dim3((unsigned)n_items), dim3(64), 0, stream, a);
-  else
-    hipLaunchKernelGGL((als_short_cg_kernel<false>), dim3((unsigned)n_items), dim3(64), 0, stream, a);
-  return hipGetLastError();
+  return launch_kernel(a.f > 64 ? als_short_cg_kernel<true> : als_short_cg_kernel<false>, dim3((unsigned)n_items), dim3(64),
+                       0, stream, a);
 }
 
 }  // namespace cumf

@@ -2264,27 +2264,18 @@ __global__ __launch_bounds__(64 * NW, NB >= 10 ? 1 : 2) void als_wave_multi_kern
 #ifndef CUMF_WAVE_PART
 #define CUMF_WAVE_PART 0
 #endif
-template <int NB>
-hipError_t wave_lu_launch(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream);
 
 #if CUMF_WAVE_PART == 0
 template <int NB>
-hipError_t wave_solve_launch(const KernelArgs& a, int mode, long n_rows, hipStream_t stream);
-template <>
-hipError_t wave_solve_launch<CUMF_WAVE_NB>(const KernelArgs& a, int mode, long n_rows, hipStream_t stream) {
+hipError_t wave_solve_launch(const KernelArgs& a, int mode, long n_rows, hipStream_t stream) {
   if (n_rows <= 0) return hipSuccess;
-  if (mode != kModeCG) {
-    return hipErrorInvalidValue;  // LU / materialise of dumped tiles: als_reduce_kernel (als_kernels.hip)
-  } else if (mode == kModeCG) {
-    // the tiles are VALU operands (VGPRs only): 91 tiles at NB = 13 = four waves x 23 tiles next to the five
-    // vectors, at two waves per SIMD
-    constexpr int NW = CUMF_WAVE_NB >= 10 ? 4 : 1;
-    const size_t lds = NW > 1 ? (size_t)NW * CUMF_WAVE_NB * 16 * sizeof(float) : 0;
-    hipLaunchKernelGGL((als_wave_cg_kernel<CUMF_WAVE_NB, NW>), dim3((unsigned)n_rows), dim3(64 * NW), lds, stream, a);
-  }
-  return hipGetLastError();
+  if (mode != kModeCG) return hipErrorInvalidValue;  // LU / materialise of dumped tiles: als_reduce_kernel (als_kernels.hip)
+  // the tiles are VALU operands (VGPRs only): 91 tiles at NB = 13 = four waves x 23 tiles next to the five
+  // vectors, at two waves per SIMD
+  constexpr int NW = NB >= 10 ? 4 : 1;
+  const size_t lds = NW > 1 ? (size_t)NW * NB * 16 * sizeof(float) : 0;
+  return launch_kernel(als_wave_cg_kernel<NB, NW>, dim3((unsigned)n_rows), dim3(64 * NW), lds, stream, a);
 }
-
 #endif  // CUMF_WAVE_PART == 0
 
 
@@ -2324,76 +2315,59 @@ static hipError_t launch_wave_lu_w(const KernelArgs& a, long n_items, hipStream_
   const size_t stage_lds = wave_stage_lds_floats<NB, ARITH>() * sizeof(float);
   const size_t lu_lds = wave_lu_lds_floats<NB>(a.f) * sizeof(float);
   const size_t lds = lu_lds > stage_lds ? lu_lds : stage_lds;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  note_item_kernel(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>));
-  hipLaunchKernelGGL((als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>), dim3((unsigned)n_items), dim3(64), lds, stream, a);
-  return hipGetLastError();
+  return launch_item_kernel(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>, dim3((unsigned)n_items), dim3(64), lds, stream, a);
 }
 // whole: no item of this launch dumps partial tiles (WHOLE: the instance without the dump exit)
-template <>
-hipError_t wave_lu_launch<CUMF_WAVE_NB>(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream) {
+template <int NB>
+hipError_t wave_lu_launch(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream) {
   return with_arith(r, [&](auto arith, auto fc) {
     constexpr int ARITH = decltype(arith)::value, FC = decltype(fc)::value;
-    return whole ? launch_wave_lu_w<CUMF_WAVE_NB, FC, ARITH, true>(a, n_items, stream)
-                 : launch_wave_lu_w<CUMF_WAVE_NB, FC, ARITH, false>(a, n_items, stream);
+    return whole ? launch_wave_lu_w<NB, FC, ARITH, true>(a, n_items, stream)
+                 : launch_wave_lu_w<NB, FC, ARITH, false>(a, n_items, stream);
   });
 }
 #endif
 
 #if CUMF_WAVE_PART == 0
 // ----------------------------------------------------------------------------------
-// Launcher (called by launch_half_iteration, als_kernels.hip)
+// Launcher (called by launch_half_iteration, als_launch.cpp)
 // ----------------------------------------------------------------------------------
 template <int NB, int FC, int ARITH>
 static hipError_t launch_wave_fc(const KernelArgs& a, int mode, long n_items, hipStream_t stream) {
   const size_t stage_lds = wave_stage_lds_floats<NB, ARITH>() * sizeof(float);
-  if (mode == kModeMaterialize) {
-    if constexpr (ARITH != kArithSplit3) {
-      return hipErrorInvalidValue;  // materialise: the 24-bit arithmetic on the fp32 table only
-    } else {
-      note_item_kernel(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeMaterialize, FC, kArithSplit3>));
-      hipLaunchKernelGGL((als_wave_kernel<NB, kModeMaterialize, FC, kArithSplit3>), dim3((unsigned)n_items), dim3(64),
-                         stage_lds, stream, a);
-    }
+  if (mode != kModeMaterialize)
+    return launch_item_kernel(als_wave_kernel<NB, kModeCG, FC, ARITH>, dim3((unsigned)n_items), dim3(64), stage_lds, stream, a);
+  if constexpr (ARITH != kArithSplit3) {
+    return hipErrorInvalidValue;  // materialise: the 24-bit arithmetic on the fp32 table only
   } else {
-    note_item_kernel(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeCG, FC, ARITH>));
-    hipLaunchKernelGGL((als_wave_kernel<NB, kModeCG, FC, ARITH>), dim3((unsigned)n_items), dim3(64), stage_lds, stream, a);
+    return launch_item_kernel(als_wave_kernel<NB, kModeMaterialize, FC, kArithSplit3>, dim3((unsigned)n_items), dim3(64),
+                              stage_lds, stream, a);
   }
-  return hipGetLastError();
 }
 
 template <int NB>
-hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream);
-template <>
-hipError_t wave_item_launch<CUMF_WAVE_NB>(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items,
-                                          hipStream_t stream) {
+hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream) {
   if (n_items <= 0) return hipSuccess;
   if (mode != kModeMaterialize && mode != kModeLU && mode != kModeCG) return hipErrorInvalidValue;
-#if CUMF_WAVE_NB > 7
-  // two waves per item; items without a slot (whole rows) are solved in the kernel (CG, or the LU of
-  // als_lu_wg.h with two wave roles), items with one dump their tiles
-  return with_arith(r, [&](auto arith, auto) -> hipError_t {
-    constexpr int ARITH = decltype(arith)::value;
-    if (ARITH != kArithSplit3 && mode == kModeMaterialize) return hipErrorInvalidValue;
-    // double-buffered stages of dword chunks, or one stage image of the pre-split table shared by the two waves
-    size_t lds = ARITH == kArithPre ? PreGeo2<CUMF_WAVE_NB>::kBytes : 2 * wave_stage_lds_floats<CUMF_WAVE_NB>() * sizeof(float);
-    if (lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float) > lds) lds = lu_wg_lds_floats<CUMF_WAVE_NB>(a.f) * sizeof(float);
-    const auto kernel = mode == kModeCG ? als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeCG, ARITH>
-                                        : als_wave_multi_kernel<CUMF_WAVE_NB, 2, kModeLU, ARITH>;
-    note_item_kernel(reinterpret_cast<const void*>(kernel));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_items), dim3(128), lds, stream, a);
-    return hipGetLastError();
-  });
-#else
-  if (mode == kModeLU) return wave_lu_launch<CUMF_WAVE_NB>(a, r, whole, n_items, stream);  // part 1 of this file
-  return with_arith(r, [&](auto arith, auto fc) {
-    return launch_wave_fc<CUMF_WAVE_NB, decltype(fc)::value, decltype(arith)::value>(a, mode, n_items, stream);
-  });
-#endif
+  if constexpr (NB > kMaxWaveNB) {
+    // two waves per item; items without a slot (whole rows) are solved in the kernel (CG, or the LU of
+    // als_lu_wg.h with two wave roles), items with one dump their tiles
+    return with_arith(r, [&](auto arith, auto) -> hipError_t {
+      constexpr int ARITH = decltype(arith)::value;
+      if (ARITH != kArithSplit3 && mode == kModeMaterialize) return hipErrorInvalidValue;
+      // double-buffered stages of dword chunks, or one stage image of the pre-split table shared by the two waves
+      size_t lds = ARITH == kArithPre ? PreGeo2<NB>::kBytes : 2 * wave_stage_lds_floats<NB>() * sizeof(float);
+      if (lu_wg_lds_floats<NB>(a.f) * sizeof(float) > lds) lds = lu_wg_lds_floats<NB>(a.f) * sizeof(float);
+      const auto kernel = mode == kModeCG ? als_wave_multi_kernel<NB, 2, kModeCG, ARITH>
+                                          : als_wave_multi_kernel<NB, 2, kModeLU, ARITH>;
+      return launch_item_kernel(kernel, dim3((unsigned)n_items), dim3(128), lds, stream, a);
+    });
+  } else {
+    if (mode == kModeLU) return wave_lu_launch<NB>(a, r, whole, n_items, stream);  // part 1 of this file
+    return with_arith(r, [&](auto arith, auto fc) {
+      return launch_wave_fc<NB, decltype(fc)::value, decltype(arith)::value>(a, mode, n_items, stream);
+    });
+  }
 }
 
 #endif  // CUMF_WAVE_PART == 0
@@ -2401,9 +2375,7 @@ hipError_t wave_item_launch<CUMF_WAVE_NB>(const KernelArgs& a, int mode, const R
 #if CUMF_ABLATE && CUMF_WAVE_PART == 0
 // profiling build: read (and clear) the CG iteration histogram of this feature-block count's kernels
 template <int NB>
-hipError_t wave_cg_hist(unsigned long long* out16);
-template <>
-hipError_t wave_cg_hist<CUMF_WAVE_NB>(unsigned long long* out16) {
+hipError_t wave_cg_hist(unsigned long long* out16) {
   hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_cg_hist), 16 * sizeof(unsigned long long));
   if (e != hipSuccess) return e;
   const unsigned long long zero[16] = {};
@@ -2451,10 +2423,20 @@ hipError_t launch_presplit3(const float* src, void* dst, long long rows, int f, 
   if (!presplit_supported(f)) return hipErrorInvalidValue;
   const int fb = f / 16;
   const unsigned pitch = presplit_pitch(f);
-  hipLaunchKernelGGL(presplit_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src,
-                     static_cast<unsigned short*>(dst), n, f, fb, nb_for_f(f) > kMaxWaveNB ? 8 : 4, pitch / 2);
-  return hipGetLastError();
+  return launch_kernel(presplit_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src,
+                       static_cast<unsigned short*>(dst), n, f, fb, nb_for_f(f) > kMaxWaveNB ? 8 : 4, pitch / 2);
 }
+#endif
+
+// The entry points of this translation unit's NB and part (als_internal.h)
+#if CUMF_WAVE_PART == 0
+template hipError_t wave_item_launch<CUMF_WAVE_NB>(const KernelArgs&, int, const Route&, bool, long, hipStream_t);
+template hipError_t wave_solve_launch<CUMF_WAVE_NB>(const KernelArgs&, int, long, hipStream_t);
+#if CUMF_ABLATE
+template hipError_t wave_cg_hist<CUMF_WAVE_NB>(unsigned long long*);
+#endif
+#elif CUMF_WAVE_NB <= 7
+template hipError_t wave_lu_launch<CUMF_WAVE_NB>(const KernelArgs&, const Route&, bool, long, hipStream_t);
 #endif
 
 }  // namespace cumf

@@ -1,10 +1,15 @@
-"""Is the device code of two host objects the same, kernel by kernel?  python tools/kernels_equal.py A.o B.o
+"""Is the device code of two sets of host objects the same, kernel by kernel?
+    python tools/kernels_equal.py A.o B.o                  two objects
+    python tools/kernels_equal.py a1.o,a2.o,... b1.o,...   two comma-separated lists
+    python tools/kernels_equal.py DIR_A DIR_B              every *.o directly in each directory
 
-Point it at pairs of csrc/*.o, not at libALS.so: the linked library carries one offload bundle per translation unit back to
-back, and one --unbundle may see only the first.  Per kernel it compares the instructions (llvm-objdump, with branch-target
-labels, trailing comments and the PC-relative literal after each s_getpc_b64 normalised: that offset to a global such as
-g_wave_zeros moves when the kernel order changes) and the register / LDS / scratch / kernarg metadata (llvm-readelf --notes).
-Kernels present on one side only are reported.  Prints SAME or DIFFERENT (exit status 0 / 1).  No GPU needed."""
+Each side is the union of the kernels of its objects, keyed by symbol, so kernels may move between objects (a kernel that
+two objects of one side carry in different versions is reported).  Point it at csrc/*.o, not at libALS.so: the linked
+library carries one offload bundle per translation unit back to back, and one --unbundle may see only the first.  Per
+kernel it compares the instructions (llvm-objdump, with branch-target labels, trailing comments and the PC-relative
+literal after each s_getpc_b64 normalised: that offset to a global such as g_wave_zeros moves when the kernel order
+changes) and the register / LDS / scratch / kernarg metadata (llvm-readelf --notes).  Kernels present on one side only are
+reported.  Prints SAME or DIFFERENT (exit status 0 / 1).  No GPU needed."""
 import os, re, subprocess, sys, tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
@@ -15,6 +20,8 @@ META = ("agpr_count", "sgpr_count", "vgpr_count", "sgpr_spill_count", "vgpr_spil
 def code_object(obj, tmp):
     fatbin, co = os.path.join(tmp, "x.fatbin"), os.path.join(tmp, "x.co")
     subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fatbin], check=True)
+    if os.path.getsize(fatbin) == 0:  # a host-only object
+        return None
     subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fatbin}",
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
     return co
@@ -24,21 +31,31 @@ def kernels(obj):
     """{symbol: (normalised instructions, metadata)} of every kernel in obj's gfx950 code object."""
     with tempfile.TemporaryDirectory() as tmp:
         co = code_object(obj, tmp)
-        dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co],
+        if co is None:
+            return {}
+        dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co],
                              check=True, capture_output=True, text=True).stdout
+        syms = subprocess.run([f"{LLVM}/llvm-readelf", "-s", "--wide", co], check=True, capture_output=True, text=True).stdout
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
+    # end address of every function: the padding words behind a kernel (alignment of the next one) are not its code
+    end = {m.group(3): int(m.group(1), 16) + int(m.group(2), 0)  # (readelf prints large sizes in hex)
+           for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+(0x[0-9a-f]+|\d+)\s+FUNC\s+\S+\s+\S+\s+\S+\s+(\S+)$", syms, re.M)}
     code = {}
     name = None
     after_getpc = False
     for line in dis.splitlines():
-        m = re.match(r"^<(.+)>:$", line.strip())
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line.strip())
         if m:
             name = m.group(1)
             code[name] = []
             after_getpc = False
             continue
-        ins = line.split("//")[0].strip()
+        ins, _, comment = line.partition("//")
+        ins = ins.strip()
         if name is None or not ins or ins == "..." or re.match(r"^\S+:$", ins):  # "...": zero padding
+            continue
+        addr = re.match(r"\s*([0-9A-Fa-f]+):", comment)
+        if addr and name in end and int(addr.group(1), 16) >= end[name]:
             continue
         ins = re.sub(r"\s+<[^>]*>", "", ins)  # branch targets: <symbol+offset>
         if after_getpc and ins.startswith("s_add_u32"):
@@ -54,10 +71,28 @@ def kernels(obj):
     return {k: (code.get(k), meta[k]) for k in meta}
 
 
+def objects(arg):
+    if os.path.isdir(arg):
+        return sorted(os.path.join(arg, f) for f in os.listdir(arg) if f.endswith(".o"))
+    return arg.split(",")
+
+
+def side(arg, diffs):
+    """{symbol: (instructions, metadata)} over every object of one side."""
+    out = {}
+    for obj in objects(arg):
+        for k, v in kernels(obj).items():
+            if k in out and out[k] != v:
+                diffs.append(f"two versions of {k} in {arg}")
+            out[k] = v
+    return out
+
+
 def main():
     a, b = sys.argv[1], sys.argv[2]
-    ka, kb = kernels(a), kernels(b)
-    diffs = [f"only in {a}: {k}" for k in sorted(set(ka) - set(kb))] + [f"only in {b}: {k}" for k in sorted(set(kb) - set(ka))]
+    diffs = []
+    ka, kb = side(a, diffs), side(b, diffs)
+    diffs += [f"only in {a}: {k}" for k in sorted(set(ka) - set(kb))] + [f"only in {b}: {k}" for k in sorted(set(kb) - set(ka))]
     for k in sorted(set(ka) & set(kb)):
         (ca, ma), (cb, mb) = ka[k], kb[k]
         if ma != mb:
