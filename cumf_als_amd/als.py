@@ -7,6 +7,9 @@
   device-pointer entry points (torch CUDA tensors are used only as device memory).
 * `ALSEngine` keeps one dataset resident in HBM and steps half-iterations; it is what
   bench.py times and what the multi-GPU driver (`cumf_als_amd.dist`) builds on.
+* `ImplicitALSEngine` does the same for implicit feedback (include/cumf_implicit_capi.h): the
+  confidence-weighted model of Hu, Koren and Volinsky, over `implicit_gram`, `update_implicit`,
+  `implicit_loss`.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -558,6 +561,139 @@ class ALSEngine:
     def close(self) -> None:
         """Destroy the plans and hand the library's pooled scratch of this device back (up to 48 GiB of tile buffer
         at f >= 144 that lives outside torch's caching allocator)."""
+        for p in self.x_plans + self.t_plans:
+            p.close()
+        self.x_plans, self.t_plans = [], []
+        release_scratch()
+
+
+# ---------------------------------------------------------------------------------------
+# implicit feedback (include/cumf_implicit_capi.h)
+# ---------------------------------------------------------------------------------------
+
+IMPLICIT_REG_WEIGHTED, IMPLICIT_REG_PLAIN = 0, 1
+
+
+def _reg_id(reg) -> int:
+    if reg in (IMPLICIT_REG_WEIGHTED, "weighted"):
+        return IMPLICIT_REG_WEIGHTED
+    if reg in (IMPLICIT_REG_PLAIN, "plain"):
+        return IMPLICIT_REG_PLAIN
+    raise ValueError(f"unknown reg mode {reg!r} (weighted | plain)")
+
+
+def implicit_available(f: int, solver="cg") -> bool:
+    return bool(_libmod.load().cumf_implicit_available(int(f), _solver_id(solver)))
+
+
+def implicit_gram(table, G=None):
+    """G = table^T table (f x f fp32, both triangles) of a rows x f table (cumf_implicit_gram); bit-identical run to run."""
+    import torch
+
+    rows, f = int(table.shape[0]), int(table.shape[1])
+    if G is None:
+        G = torch.empty((f, f), dtype=torch.float32, device=table.device)
+    _libmod.check(_libmod.load().cumf_implicit_gram(_dp(table, torch.float32), rows, f, _dp(G, torch.float32), _stream()),
+                  "cumf_implicit_gram")
+    return G
+
+
+def get_hermitian_implicit(plan: Plan, colidx, val, gather, G, lambda_: float, alpha: float, reg="weighted", tt=None,
+                           rhs=None):
+    """The implicit systems tt[rows,f,f] = G + sum w y y^T + reg I and rhs[rows,f] = sum_{r>0} (1+w) y of the plan's rows
+    (cumf_get_hermitian_implicit)."""
+    import torch
+
+    f, rows = plan.f, plan.batch_rows
+    if tt is None:
+        tt = torch.empty((rows, f, f), dtype=torch.float32, device=gather.device)
+    if rhs is None:
+        rhs = torch.empty((rows, f), dtype=torch.float32, device=gather.device)
+    _libmod.check(_libmod.load().cumf_get_hermitian_implicit(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(gather, torch.float32), _dp(G, torch.float32),
+        _dp(tt, torch.float32), _dp(rhs, torch.float32), f, float(lambda_), float(alpha), _reg_id(reg), _stream()),
+        "cumf_get_hermitian_implicit")
+    return tt, rhs
+
+
+def update_implicit(plan: Plan, colidx, val, gather, G, update, lambda_: float, alpha: float, reg="weighted", solver="cg",
+                    cg_iters: int = 3):
+    """One implicit half-iteration over the plan's rows (cumf_als_update_implicit); `update` is the CG warm start and
+    receives the solution, G is implicit_gram(gather)."""
+    import torch
+
+    _libmod.check(_libmod.load().cumf_als_update_implicit(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(gather, torch.float32), _dp(G, torch.float32),
+        _dp(update, torch.float32), plan.f, float(lambda_), float(alpha), _reg_id(reg), _solver_id(solver), int(cg_iters),
+        _stream()), "cumf_als_update_implicit")
+    return update
+
+
+def implicit_loss(rowptr, colidx, val, XT, thetaT, lambda_: float, alpha: float, reg="weighted", out=None):
+    """The implicit objective (cumf_implicit_loss) as a 1-element fp64 tensor: rowptr/colidx/val are the CSR arrays of
+    the ratings on the device (int32), XT m x f, thetaT n x f."""
+    import torch
+
+    m, f = int(XT.shape[0]), int(XT.shape[1])
+    if out is None:
+        out = torch.zeros(1, dtype=torch.float64, device=XT.device)
+    _libmod.check(_libmod.load().cumf_implicit_loss(
+        _dp(rowptr, torch.int32), _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(XT, torch.float32),
+        _dp(thetaT, torch.float32), m, int(thetaT.shape[0]), f, float(lambda_), float(alpha), _reg_id(reg),
+        _dp(out, torch.float64), _stream()), "cumf_implicit_loss")
+    return out
+
+
+class ImplicitALSEngine:
+    """Implicit-feedback ALS on one GPU: the ratings of `r` (a `datagen.Ratings` on the device) are interaction
+    strengths -- weight alpha |r|, preference r > 0 -- and every unstored entry counts as a preference of 0 with
+    confidence 1.  Same shape as `ALSEngine`; each half-iteration forms G = Y^T Y of the fixed side once, before its
+    batches.  solver "cg" (warm-started, `cg_iters` steps; rows of at most 32 entries never form their system) or "lu";
+    reg "weighted" (lambda n_u, the default) or "plain" (lambda)."""
+
+    def __init__(self, r, f: int, lambda_: float, alpha: float, solver="cg", cg_iters: int = 3, reg="weighted",
+                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0):
+        import torch
+
+        if not implicit_available(f, solver):
+            raise ValueError(f"implicit ALS takes even 8 <= f <= 128 and solver cg | lu (got f = {f}, {solver!r})")
+        self.r, self.f, self.lam, self.alpha = r, f, float(lambda_), float(alpha)
+        self.solver, self.cg_iters, self.reg = solver, int(cg_iters), _reg_id(reg)
+        self.m, self.n = r.m, r.n
+        self.device = r.csr_indices.device
+        self.x_plans = ALSEngine._plans(self, r.csr_indptr, r.m, x_batch, chunk)
+        self.t_plans = ALSEngine._plans(self, r.csc_indptr, r.n, theta_batch, chunk)
+        self.csr_rowptr = r.csr_indptr.to(device=self.device, dtype=torch.int32).contiguous()
+        self.thetaT = torch.zeros((r.n, f), dtype=torch.float32, device=self.device)
+        self.XT = torch.zeros((r.m, f), dtype=torch.float32, device=self.device)
+        self.G = torch.empty((f, f), dtype=torch.float32, device=self.device)
+
+    def init_factors(self, thetaT=None, XT=None, seed: int = 0):
+        ALSEngine.init_factors(self, thetaT, XT, seed)
+
+    def _half(self, plans, colidx, val, gather, update):
+        implicit_gram(gather, self.G)
+        for p in plans:
+            update_implicit(p, colidx, val, gather, self.G, update, self.lam, self.alpha, self.reg, self.solver,
+                            self.cg_iters)
+
+    def update_x(self):
+        self._half(self.x_plans, self.r.csr_indices, self.r.csr_data, self.thetaT, self.XT)
+
+    def update_theta(self):
+        self._half(self.t_plans, self.r.csc_indices, self.r.csc_data, self.XT, self.thetaT)
+
+    def iterate(self, iters: int = 1):
+        for _ in range(iters):
+            self.update_x()
+            self.update_theta()
+
+    def loss(self) -> float:
+        """The implicit objective of the current factors (fp64)."""
+        return float(implicit_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.XT, self.thetaT, self.lam,
+                                   self.alpha, self.reg).item())
+
+    def close(self) -> None:
         for p in self.x_plans + self.t_plans:
             p.close()
         self.x_plans, self.t_plans = [], []

@@ -274,6 +274,116 @@ hipError_t with_nb(int nb, Go&& go) {
     return nb == LO ? go(std::integral_constant<int, LO>{}) : with_nb<LO + 1, HI>(nb, go);
 }
 
+// Scratch that outlives a call (als_plan.cpp): process-wide, grow-only, one buffer per (device, stream, kind); an entry
+// point that takes pooled scratch holds a ScratchLease until its last launch is enqueued (cumf_release_scratch waits for it).
+enum {
+  kScratchTiles = 0,
+  kScratchWords = 1,
+  kScratchPlanes = 2,
+  // implicit feedback (als_implicit.cpp): Gram partials, per-chunk partial systems, materialised systems, right-hand sides,
+  // compact solution vectors, fp64 Grams + loss partials
+  kScratchImpGram = 3,
+  kScratchImpSlots = 4,
+  kScratchImpTT = 5,
+  kScratchImpRhs = 6,
+  kScratchImpX = 7,
+  kScratchImpAux = 8,
+};
+int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
+struct ScratchLease {
+  int dev = 0;
+  ScratchLease();
+  ~ScratchLease();
+  ScratchLease(const ScratchLease&) = delete;
+  ScratchLease& operator=(const ScratchLease&) = delete;
+};
+// ---- Implicit feedback (als_implicit.hip kernels, als_implicit.cpp host side; include/cumf_implicit_capi.h)
+constexpr int kImpGramSlab = 1024;    // table rows per workgroup of the Gram kernel (one fp32 partial each)
+constexpr int kImpLossBlocks = 1024;  // workgroups of the loss pass (one fp64 partial each)
+constexpr int kImpRegPlain = 1;       // CUMF_IMPLICIT_REG_PLAIN (reg_u = lambda); else lambda n_u
+struct ImplicitArgs {
+  // items of the materialising kernel / the short-row CG (the plan's lists); item_dst: system index of an item's row
+  // (nullptr: row - row_begin)
+  const int* item_row;
+  const long long* item_begin;
+  const int* item_len;
+  const int* item_slot;
+  const int* item_rowlen;
+  const int* item_dst;
+  // rows cut into chunks (slot reduce); mrow_dst as item_dst
+  const int* mrow_row;
+  const int* mrow_slot0;
+  const int* mrow_nslots;
+  const int* mrow_rowlen;
+  const int* mrow_dst;
+  long long row_begin;
+  const int* colidx;
+  const float* val;
+  const float* gather;
+  const float* G;  // f x f Gram of `gather`
+  float* tt;       // systems, f x f each
+  float* rhs;      // right-hand sides (may be null)
+  float* slots;    // per-chunk partials, f x f + f each
+  float* update;   // short-row CG: warm start in, solution out
+  int f;
+  float lambda, alpha;
+  int reg_mode;
+  int cg_iters;
+};
+size_t implicit_gram_part_floats(long rows, int f);
+// G (fp32, may be null) and G64 (fp64, may be null) of a rows x f table; part: implicit_gram_part_floats floats
+hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, float* G, double* G64, hipStream_t stream);
+// systems of items [0, n_items) of a's lists, then the n_mrows chunked rows
+hipError_t launch_implicit_hermitian(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream);
+// Gram-free CG of the whole rows of items [first, first + count) (at most kShortRow entries each)
+hipError_t launch_implicit_short_cg(const ImplicitArgs& a, long first, long count, hipStream_t stream);
+hipError_t launch_implicit_copy_rows(const int* rows, long count, int f, const float* in, float* out, bool scatter,
+                                     hipStream_t stream);
+hipError_t launch_implicit_zero_rows(const int* rows, long count, int f, float* x, hipStream_t stream);
+// part: kImpLossBlocks doubles
+hipError_t launch_implicit_loss(const int* rowptr, const int* colidx, const float* val, const float* XT, const float* thetaT,
+                                long m, int f, float lambda, float alpha, int reg_mode, const double* Gx, const double* Gy,
+                                double* part, double* out, hipStream_t stream);
+// Work lists of the implicit-feedback half-iterations, built on a plan at first use (als_implicit.cpp).
+struct ImplicitLists;
+void free_implicit_lists(ImplicitLists* lists);
+
+}  // namespace cumf
+
+// A half-iteration plan (cumf_plan_create, als_plan.cpp).
+struct cumf_plan {
+  long rows = 0, row_begin = 0, row_end = 0;
+  int f = 0, nb = 0, chunk = 0;
+  long long plan_nnz = 0;  // ratings of the planned rows
+  long long chunk_nnz = 0;  // ... of which in chunked rows
+  long n_items = 0, n_slots = 0, n_mrows = 0;
+  long n_short = 0;  // whole rows of at most kShortRow ratings: the last n_short items (and the last of the w list)
+  int* d_item_row = nullptr;
+  long long* d_item_begin = nullptr;
+  int* d_item_len = nullptr;
+  int* d_item_slot = nullptr;
+  int* d_item_rowlen = nullptr;
+  int* d_mrow_row = nullptr;
+  int* d_mrow_slot0 = nullptr;
+  int* d_mrow_nslots = nullptr;
+  int* d_mrow_rowlen = nullptr;
+  float* d_part = nullptr;
+  char* d_block = nullptr;  // the device block all the index arrays below and above point into
+  // chunk-only / whole-row-only item lists and the dense-slot tile buffer of the batched
+  // "Gram -> tiles -> solver kernel" path (CG on the wave kernels' Gram)
+  long n_citems = 0, n_witems = 0;
+  int *d_c_row = nullptr, *d_c_len = nullptr, *d_c_slot = nullptr, *d_c_rowlen = nullptr;
+  long long* d_c_begin = nullptr;
+  int *d_w_row = nullptr, *d_w_len = nullptr, *d_w_rowlen = nullptr;
+  long long* d_w_begin = nullptr;
+  // gram mode "fast": rows of the gather table (cumf_plan_set_gather_rows)
+  long gather_rows = 0;
+  // implicit feedback: the long-row / empty-row lists of als_implicit.cpp (built on first use, freed with the plan)
+  cumf::ImplicitLists* implicit = nullptr;
+};
+
+namespace cumf {
+
 // One launch: the dynamic-LDS opt-in above 64 KB, the launch, its error.  launch_item_kernel (NOTE): a Gram(+solve)
 // kernel, also recorded for cumf_last_kernel_name.
 template <bool NOTE = false, typename... P, typename... A>

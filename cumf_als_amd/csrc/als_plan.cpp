@@ -30,34 +30,6 @@
 
 using namespace cumf;
 
-struct cumf_plan {
-  long rows = 0, row_begin = 0, row_end = 0;
-  int f = 0, nb = 0, chunk = 0;
-  long long plan_nnz = 0;  // ratings of the planned rows
-  long long chunk_nnz = 0;  // ... of which in chunked rows
-  long n_items = 0, n_slots = 0, n_mrows = 0;
-  long n_short = 0;  // whole rows of at most kShortRow ratings: the last n_short items (and the last of the w list)
-  int* d_item_row = nullptr;
-  long long* d_item_begin = nullptr;
-  int* d_item_len = nullptr;
-  int* d_item_slot = nullptr;
-  int* d_item_rowlen = nullptr;
-  int* d_mrow_row = nullptr;
-  int* d_mrow_slot0 = nullptr;
-  int* d_mrow_nslots = nullptr;
-  int* d_mrow_rowlen = nullptr;
-  float* d_part = nullptr;
-  char* d_block = nullptr;  // the device block all the index arrays below and above point into
-  // chunk-only / whole-row-only item lists and the dense-slot tile buffer of the batched
-  // "Gram -> tiles -> solver kernel" path (CG on the wave kernels' Gram)
-  long n_citems = 0, n_witems = 0;
-  int *d_c_row = nullptr, *d_c_len = nullptr, *d_c_slot = nullptr, *d_c_rowlen = nullptr;
-  long long* d_c_begin = nullptr;
-  int *d_w_row = nullptr, *d_w_len = nullptr, *d_w_rowlen = nullptr;
-  long long* d_w_begin = nullptr;
-  // gram mode "fast": rows of the gather table (cumf_plan_set_gather_rows)
-  long gather_rows = 0;
-};
 
 namespace {
 
@@ -282,6 +254,7 @@ extern "C" int cumf_plan_destroy(cumf_plan_t* p) {
   if (!p) return 0;
   if (p->d_block) (void)hipFree(p->d_block);  // every index array lives in this one block
   if (p->d_part) (void)hipFree(p->d_part);
+  free_implicit_lists(p->implicit);
   delete p;
   return 0;
 }
@@ -307,7 +280,6 @@ namespace {
 // copy of the gather table (gram mode "fast").  Process-wide, grow-only, one buffer per (device, stream, kind):
 // calls on one stream are ordered, so the X_BATCH / THETA_BATCH plans of doALS and the pipeline pieces of
 // DistALS share ONE buffer instead of keeping one each.  cumf_release_scratch frees them.
-enum { kScratchTiles = 0, kScratchWords = 1, kScratchPlanes = 2 };
 struct Scratch {
   void* ptr = nullptr;
   size_t cap = 0;
@@ -322,25 +294,23 @@ std::map<int, int*> g_fast_flag;  // per device (range report of gram mode "fast
 // enqueued kernels finish) and frees that device's entries only.
 std::map<int, int> g_scratch_users;
 std::condition_variable g_scratch_cv;
-struct ScratchLease {
-  int dev = 0;
-  ScratchLease() {
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(g_scratch_mutex);
-    ++g_scratch_users[dev];
-  }
-  ~ScratchLease() {
-    {
-      std::lock_guard<std::mutex> lock(g_scratch_mutex);
-      --g_scratch_users[dev];
-    }
-    g_scratch_cv.notify_all();
-  }
-  ScratchLease(const ScratchLease&) = delete;
-  ScratchLease& operator=(const ScratchLease&) = delete;
-};
 
-int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out) {
+}  // namespace
+
+cumf::ScratchLease::ScratchLease() {
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(g_scratch_mutex);
+  ++g_scratch_users[dev];
+}
+cumf::ScratchLease::~ScratchLease() {
+  {
+    std::lock_guard<std::mutex> lock(g_scratch_mutex);
+    --g_scratch_users[dev];
+  }
+  g_scratch_cv.notify_all();
+}
+
+int cumf::scratch_get(hipStream_t stream, int kind, size_t bytes, void** out) {
   int dev = 0;
   CUMF_HIP_CHECK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lock(g_scratch_mutex);
@@ -358,6 +328,8 @@ int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out) {
   *out = sc.ptr;
   return 0;
 }
+
+namespace {
 
 int fast_flag_get(int** out) {
   int dev = 0;

@@ -30,58 +30,6 @@ namespace {
 // zeros that stand in for the factor row of a lane without a rating
 __device__ __attribute__((aligned(16))) float g_short_zeros[256];
 
-template <int CTRL, int BANK_MASK>
-__device__ __forceinline__ float dpp_move(float old, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL,
-                                                               0xf, BANK_MASK, false));
-}
-// the value of lane L ^ X (X = 1, 2, 4, 8, 16, 32)
-template <int X>
-__device__ __forceinline__ float lane_xor(float v, int lane) {
-  if constexpr (X == 1) return dpp_move<0xB1, 0xf>(0.f, v);   // quad_perm [1,0,3,2]
-  if constexpr (X == 2) return dpp_move<0x4E, 0xf>(0.f, v);   // quad_perm [2,3,0,1]
-  if constexpr (X == 4)                                        // row_shr:4 into the banks with bit 2 set, row_shl:4 into the others
-    return dpp_move<0x104, 0x5>(dpp_move<0x114, 0xa>(0.f, v), v);
-  if constexpr (X == 8) return dpp_move<0x128, 0xf>(0.f, v);  // row_ror:8
-  if constexpr (X == 16) return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));
-  if constexpr (X == 32)
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (lane ^ 32), __builtin_bit_cast(int, v)));
-}
-// Sums of N registers over the wave, transposed: lane L ends with the full sum of register L mod N.
-template <int N>
-__device__ __forceinline__ float reduce_transposed(float (&P)[N], int lane) {
-  static_assert(N == 8 || N == 16 || N == 32, "register count");
-  auto step = [&](auto xc, auto mc) {  // M registers -> M / 2: the lane keeps register 2 m + bit, hands 2 m + !bit to lane ^ X
-    constexpr int X = decltype(xc)::value, M = decltype(mc)::value;
-    const bool bit = (lane & X) != 0;
-#pragma unroll
-    for (int m = 0; m < M / 2; ++m) {
-      const float keep = bit ? P[2 * m + 1] : P[2 * m], send = bit ? P[2 * m] : P[2 * m + 1];
-      P[m] = keep + lane_xor<X>(send, lane);
-    }
-  };
-  auto ic = [](auto v) { return v; };
-  (void)ic;
-  step(std::integral_constant<int, 1>{}, std::integral_constant<int, N>{});
-  step(std::integral_constant<int, 2>{}, std::integral_constant<int, N / 2>{});
-  step(std::integral_constant<int, 4>{}, std::integral_constant<int, N / 4>{});
-  float v;
-  if constexpr (N == 8) {
-    v = P[0];
-    v += lane_xor<8>(v, lane);
-    v += lane_xor<16>(v, lane);
-  } else if constexpr (N == 16) {
-    step(std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
-    v = P[0];
-    v += lane_xor<16>(v, lane);
-  } else {
-    step(std::integral_constant<int, 8>{}, std::integral_constant<int, 4>{});
-    step(std::integral_constant<int, 16>{}, std::integral_constant<int, 2>{});
-    v = P[0];
-  }
-  return v + lane_xor<32>(v, lane);
-}
-
 // the whole row with at most N ratings in flight (N = 8, 16, 32 >= n); TWO: f > 64, the lanes hold two features each
 template <bool TWO, int N>
 __device__ __forceinline__ void short_cg_row(const KernelArgs& a, int row, int n, float rv, const float* grow, int lane) {

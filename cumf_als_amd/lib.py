@@ -1,4 +1,5 @@
-"""ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h).
+"""ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h, cumf_dist_capi.h and
+cumf_implicit_capi.h).
 
 The library is the product: there is no Python or CPU fallback.  `load()` raises
 when the shared object is missing or lacks a declared symbol.
@@ -31,6 +32,11 @@ DIST_SYMBOLS = [
     "cumf_dist_gather_create", "cumf_dist_gather_update", "cumf_dist_gather_destroy",
     "cumf_dist_reduce_create", "cumf_dist_reduce_update_theta", "cumf_dist_reduce_destroy",
 ]
+# every extern "C" symbol declared in include/cumf_implicit_capi.h (implicit feedback, als_implicit.cpp)
+IMPLICIT_SYMBOLS = [
+    "cumf_implicit_available", "cumf_implicit_gram", "cumf_get_hermitian_implicit", "cumf_als_update_implicit",
+    "cumf_implicit_loss",
+]
 # C++-linkage drop-in symbols (include/als.h, include/cg.h) under the reference's mangled names
 CXX_SYMBOLS = [
     "_Z5doALSPKiS0_PKfS0_S0_S2_S0_PfS3_S0_S0_S2_iiillfiiii",
@@ -60,7 +66,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  cumf_als_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols declared in include/: {missing}")
 
@@ -170,6 +176,19 @@ def load():
     lib.cumf_dist_reduce_update_theta.argtypes = [vp, vp, ip, fp, fp, fp, C.c_float, C.c_int, C.c_int, fp, vp, vp]
     lib.cumf_dist_reduce_destroy.restype = C.c_int
     lib.cumf_dist_reduce_destroy.argtypes = [vp]
+    # include/cumf_implicit_capi.h
+    lib.cumf_implicit_available.restype = C.c_int
+    lib.cumf_implicit_available.argtypes = [C.c_int, C.c_int]
+    lib.cumf_implicit_gram.restype = C.c_int
+    lib.cumf_implicit_gram.argtypes = [fp, C.c_long, C.c_int, fp, vp]
+    lib.cumf_get_hermitian_implicit.restype = C.c_int
+    lib.cumf_get_hermitian_implicit.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.c_int, C.c_float, C.c_float, C.c_int, vp]
+    lib.cumf_als_update_implicit.restype = C.c_int
+    lib.cumf_als_update_implicit.argtypes = [vp, ip, fp, fp, fp, fp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                             C.c_int, vp]
+    lib.cumf_implicit_loss.restype = C.c_int
+    lib.cumf_implicit_loss.argtypes = [ip, ip, fp, fp, fp, C.c_long, C.c_long, C.c_int, C.c_float, C.c_float, C.c_int, vp,
+                                       vp]
     host_args = [vp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_float, C.c_int, C.c_int, C.c_int,
                              C.c_int]
     lib.cumf_doALS.restype = C.c_float

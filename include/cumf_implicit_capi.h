@@ -1,0 +1,62 @@
+/*
+ * cumf_implicit_capi.h -- C ABI of the implicit-feedback ALS of libALS.so (Hu, Koren, Volinsky, "Collaborative
+ * Filtering for Implicit Feedback Datasets", ICDM 2008; the `implicitPrefs` mode of Spark MLlib's ALS).
+ *
+ * A stored entry (u, i, r) has the confidence weight w = alpha |r| and the preference p = (r > 0); an unstored entry has
+ * weight 0 (confidence 1) and preference 0.  Updating the rows X from the fixed table Y (n x f, `gather`):
+ *   A_u = G + sum_{i in R(u)} w_ui y_i y_i^T + reg_u I,   G = Y^T Y over ALL rows of Y,
+ *   b_u = sum_{i in R(u), r > 0} (1 + w_ui) y_i,
+ * reg_u = lambda n_u (CUMF_IMPLICIT_REG_WEIGHTED, n_u = stored entries of row u) or lambda (CUMF_IMPLICIT_REG_PLAIN).
+ * Rows without stored entries get x_u = 0.  The other side uses the same formulas on the CSC arrays.
+ *
+ * Conventions of cumf_als_capi.h: DEVICE pointers of the calling process, `stream` a hipStream_t passed as void* (NULL =
+ * the default stream), 0 on success or a HIP error code after printing file/line to stderr, no CPU fallback.  Plans are
+ * the cumf_plan_t of cumf_als_capi.h.  Scope: even f with 8 <= f <= 128 on one GPU; anything else is refused.  Every
+ * result is bit-identical from run to run (fixed-order reductions, no float atomics).
+ */
+#ifndef CUMF_IMPLICIT_CAPI_H_
+#define CUMF_IMPLICIT_CAPI_H_
+
+#include "cumf_als_capi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+enum { CUMF_IMPLICIT_REG_WEIGHTED = 0, CUMF_IMPLICIT_REG_PLAIN = 1 };
+
+/* 1 when the implicit entry points take (f, solver): even f in [8, 128], solver CUMF_SOLVER_CG or CUMF_SOLVER_LU. */
+int cumf_implicit_available(int f, int solver);
+
+/* G = table^T table of a rows x f fp32 table: f x f fp32, both triangles, exactly symmetric.  fp32 matrix-pipe products
+ * per slab of rows, the slab partials summed in slab order in fp64. */
+int cumf_implicit_gram(const float* table, long rows, int f, float* G, void* stream);
+
+/* The materialised systems of the plan's rows: tt receives (row_end - row_begin) x f x f fp32 (row-major, both
+ * triangles; the layout of cumf_get_hermitian), rhs (row_end - row_begin) x f.  G: the f x f Gram of `gather`
+ * (cumf_implicit_gram).  Rows cut into chunks by the plan are summed over per-chunk partials in chunk order. */
+int cumf_get_hermitian_implicit(const cumf_plan_t* plan, const int* colidx, const float* val, const float* gather,
+                                const float* G, float* tt, float* rhs, int f, float lambda, float alpha, int reg_mode,
+                                void* stream);
+
+/* One implicit half-iteration over the plan's rows; update (rows x f) is the CG warm start and receives the solution.
+ *   CUMF_SOLVER_CG: rows of at most 32 stored entries run a CG that never forms A_u (A p = G p + T^T (w o T p) + reg p,
+ *                   T the row's gathered block); longer rows are materialised and solved by cumf_cg_solve_batched.  The
+ *                   recurrence of cumf_cg_solve_batched: warm start, at most cg_iters steps, exit when r.r < 1e-4.
+ *   CUMF_SOLVER_LU: every row materialised and solved by cumf_lu_solve_batched.
+ * Rows without stored entries are set to 0 by both. */
+int cumf_als_update_implicit(const cumf_plan_t* plan, const int* colidx, const float* val, const float* gather,
+                             const float* G, float* update, int f, float lambda, float alpha, int reg_mode, int solver,
+                             int cg_iters, void* stream);
+
+/* The implicit objective into *out (one DEVICE double):
+ *   L = sum_{all u,i} c_ui (p_ui - x_u.y_i)^2 + sum_u reg_u |x_u|^2 + sum_i reg_i |y_i|^2
+ *     = <X^T X, Y^T Y>_F + sum_stored [(1 + w)(p - s)^2 - s^2] + regs,   s = x_u.y_i,
+ * from the CSR arrays of the ratings (rowptr: m + 1 ints), XT (m x f) and thetaT (n x f), fp64 accumulation. */
+int cumf_implicit_loss(const int* rowptr, const int* colidx, const float* val, const float* XT, const float* thetaT,
+                       long m, long n, int f, float lambda, float alpha, int reg_mode, double* out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CUMF_IMPLICIT_CAPI_H_ */
