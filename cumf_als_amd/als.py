@@ -10,6 +10,9 @@
 * `ImplicitALSEngine` does the same for implicit feedback (include/cumf_implicit_capi.h): the
   confidence-weighted model of Hu, Koren and Volinsky, over `implicit_gram`, `update_implicit`,
   `implicit_loss`.
+* `topk`, `ranking_metrics` (include/cumf_topk_capi.h): the k best candidates per query, scored by a fused HIP kernel
+  that never writes the score matrix, and precision / recall / NDCG@k against held-out entries; both engines expose them
+  as `recommend(k, side)` and `ranking_metrics(k, side)`.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -457,7 +460,101 @@ def release_scratch() -> None:
     _libmod.check(_libmod.load().cumf_release_scratch(), "cumf_release_scratch")
 
 
-class ALSEngine:
+# ---------------------------------------------------------------------------------------
+# top-k recommendation and ranking metrics (include/cumf_topk_capi.h)
+# ---------------------------------------------------------------------------------------
+
+def topk_available(f: int, k: int) -> bool:
+    return bool(_libmod.load().cumf_topk_available(int(f), int(k)))
+
+
+def _rowptr(rowptr):
+    import torch
+
+    if rowptr.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"row pointers must be int32 or int64, got {rowptr.dtype}")
+    return _dp(rowptr), int(rowptr.dtype == torch.int64)
+
+
+def topk(query, cand, k: int, exclude=None, out=None):
+    """The k best candidates of every query row (cumf_topk): `query` rows x f and `cand` ncand x f fp32 on the device, the
+    score of a candidate the fp32 fmaf chain of the dot product in increasing feature order.  `exclude` is an optional
+    (rowptr, colidx) CSR of candidate indices per query (ascending within each row) that are never returned.  Returns
+    (ids int32, scores fp32), rows x k each, best first (ties: lower index first); missing slots are -1 / -inf."""
+    import torch
+
+    rows, f = int(query.shape[0]), int(query.shape[1])
+    if int(cand.shape[1]) != f:
+        raise ValueError(f"query and candidate tables differ in f ({f} vs {int(cand.shape[1])})")
+    if out is None:
+        out = (torch.empty((rows, k), dtype=torch.int32, device=query.device),
+               torch.empty((rows, k), dtype=torch.float32, device=query.device))
+    ids, scores = out
+    rp, rp64, ci = None, 0, None
+    if exclude is not None:
+        rp, rp64 = _rowptr(exclude[0])
+        ci = _dp(exclude[1], torch.int32)
+    _libmod.check(_libmod.load().cumf_topk(
+        _dp(query, torch.float32), rows, _dp(cand, torch.float32), int(cand.shape[0]), f, rp, rp64, ci, int(k),
+        _dp(ids, torch.int32), _dp(scores, torch.float32), _stream()), "cumf_topk")
+    return ids, scores
+
+
+def ranking_metrics(ids, test_rowptr, test_colidx, test_val=None) -> dict:
+    """precision@k, recall@k and NDCG@k (cumf_ranking_metrics) of `ids` (rows x k, as `topk` returns them) against a
+    held-out CSR per query (column indices ascending and unique within each row); an entry is relevant when its value
+    is > 0, or always without values.  Means over the queries with at least one relevant entry ("queries")."""
+    import torch
+
+    rows, k = int(ids.shape[0]), int(ids.shape[1])
+    out = torch.zeros(4, dtype=torch.float64, device=ids.device)
+    rp, rp64 = _rowptr(test_rowptr)
+    _libmod.check(_libmod.load().cumf_ranking_metrics(
+        _dp(ids, torch.int32), rows, k, rp, rp64, _dp(test_colidx, torch.int32),
+        None if test_val is None else _dp(test_val, torch.float32), _dp(out, torch.float64), _stream()),
+        "cumf_ranking_metrics")
+    n, p, r, g = out.tolist()
+    return {"queries": int(n), "precision": p, "recall": r, "ndcg": g}
+
+
+def heldout_csr(row, col, val, rows: int):
+    """(rowptr int64, colidx int32, val fp32) of a COO set, sorted by (row, col) with a torch sort: the held-out CSR of
+    `ranking_metrics`.  Pass (col, row) for the CSC."""
+    import torch
+
+    key = (row.to(torch.int64) << 32) + col.to(torch.int64)
+    order = torch.sort(key).indices
+    rowptr = torch.zeros(rows + 1, dtype=torch.int64, device=row.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(row.to(torch.int64), minlength=rows), 0)
+    return rowptr, col[order].to(torch.int32).contiguous(), val[order].to(torch.float32).contiguous()
+
+
+class _Recommender:
+    """recommend / ranking_metrics of a trained engine (`XT`, `thetaT`, ratings `r`), shared by both engines.  Side "x":
+    the rows of XT are the queries and the rows of thetaT the candidates, the training CSR excluded; side "theta" the
+    other way round, the CSC excluded."""
+
+    def _side(self, side):
+        r = self.r
+        if side == "x":
+            return self.XT, self.thetaT, (r.csr_indptr, r.csr_indices), (r.test_row, r.test_col, self.m)
+        if side == "theta":
+            return self.thetaT, self.XT, (r.csc_indptr, r.csc_indices), (r.test_col, r.test_row, self.n)
+        raise ValueError(f"side must be 'x' or 'theta', got {side!r}")
+
+    def recommend(self, k: int, side: str = "x", exclude_seen: bool = True):
+        """(ids, scores) of the k best candidates of every query row of `side`, leaving out its training entries."""
+        query, cand, seen, _ = self._side(side)
+        return topk(query, cand, k, seen if exclude_seen else None)
+
+    def ranking_metrics(self, k: int, side: str = "x", exclude_seen: bool = True) -> dict:
+        """ranking_metrics of recommend(k, side) against the engine's test set."""
+        ids, _ = self.recommend(k, side, exclude_seen)
+        row, col, rows = self._side(side)[3]
+        return ranking_metrics(ids, *heldout_csr(row, col, self.r.test_data, rows))
+
+
+class ALSEngine(_Recommender):
     """A dataset resident in HBM + the two half-iteration plans (single GPU).
 
     `r` is a `cumf_als_amd.datagen.Ratings` already on the device.  Factors are the
@@ -644,7 +741,7 @@ def implicit_loss(rowptr, colidx, val, XT, thetaT, lambda_: float, alpha: float,
     return out
 
 
-class ImplicitALSEngine:
+class ImplicitALSEngine(_Recommender):
     """Implicit-feedback ALS on one GPU: the ratings of `r` (a `datagen.Ratings` on the device) are interaction
     strengths -- weight alpha |r|, preference r > 0 -- and every unstored entry counts as a preference of 0 with
     confidence 1.  Same shape as `ALSEngine`; each half-iteration forms G = Y^T Y of the fixed side once, before its

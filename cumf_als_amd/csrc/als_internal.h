@@ -288,6 +288,10 @@ enum {
   kScratchImpRhs = 6,
   kScratchImpX = 7,
   kScratchImpAux = 8,
+  // top-k (als_topk.cpp): per-workgroup lists + survivor buffers, partial lists of the slabs, per-query metrics
+  kScratchTopkWork = 9,
+  kScratchTopkPart = 10,
+  kScratchTopkMetrics = 11,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 struct ScratchLease {
@@ -347,6 +351,42 @@ hipError_t launch_implicit_loss(const int* rowptr, const int* colidx, const floa
 // Work lists of the implicit-feedback half-iterations, built on a plan at first use (als_implicit.cpp).
 struct ImplicitLists;
 void free_implicit_lists(ImplicitLists* lists);
+
+// ---- Top-k recommendation and ranking metrics (als_topk.hip kernels, als_topk.cpp host side; include/cumf_topk_capi.h)
+constexpr int kTopkThreads = 256;         // four waves
+constexpr int kTopkQW = 32;               // queries per wave (two 16-row MFMA tiles)
+constexpr int kTopkQB = 4 * kTopkQW;      // queries per workgroup
+constexpr int kTopkNC = 64;               // candidates per LDS block (four 16-column tiles; one 64-bit exclusion mask)
+constexpr int kTopkJC = 128;              // features per LDS chunk
+constexpr int kTopkPitch = kTopkJC + 4;   // LDS row pitch: the 16 rows one k-group reads start 4 banks apart
+constexpr int kTopkBuf = 128;             // survivor buffer per query (merged when above kTopkBuf - kTopkNC)
+constexpr int kTopkMaxK = 128;
+constexpr int kTopkMaxF = 512;
+struct TopkArgs {
+  const float* Q;
+  long long rows;
+  const float* C;
+  long long ncand;
+  int f, k;
+  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
+  int rowptr64;
+  const int* excl_colidx;
+  int vec;                  // C rows may be read as float4 (f % 4 == 0, 16-byte aligned)
+  int nslab;
+  long long slab_len;       // candidates per slab, a multiple of kTopkNC
+  long long n_items;        // query blocks x slabs
+  unsigned long long* work; // per workgroup: kTopkQB x (k + kTopkBuf) keys
+  unsigned long long* part; // nslab > 1: nslab x rows x k keys
+  int* ids;                 // nslab == 1: the result
+  float* scores;
+};
+int topk_score_occupancy(bool multi);  // workgroups per CU of the score kernel
+hipError_t launch_topk_score(const TopkArgs& a, long long grid, hipStream_t stream);
+hipError_t launch_topk_merge(const unsigned long long* part, long long rows, int k, int nslab, int* ids, float* scores,
+                             hipStream_t stream);
+// part: 4 x rows doubles; out: (count, precision, recall, ndcg)
+hipError_t launch_topk_metrics(const int* ids, long long rows, int k, const void* rowptr, int rowptr64, const int* colidx,
+                               const float* val, double* part, double* out, hipStream_t stream);
 
 }  // namespace cumf
 

@@ -1,0 +1,108 @@
+// als_topk.cpp -- host side of top-k recommendation and ranking metrics (include/cumf_topk_capi.h): argument checks, the slab
+// cut, scratch, launches.  Kernels: als_topk.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+
+#include "als_internal.h"
+#include "cumf_topk_capi.h"
+
+using namespace cumf;
+
+namespace {
+
+constexpr long long kTopkMinSlab = 16 * kTopkNC;  // candidates per slab at least: the list fill stays a small part of a slab
+
+// How the score kernel cuts the work, decided here only: query blocks of kTopkQB x slabs of the candidates, on a persistent
+// grid of at most one workgroup per resident slot.  A query block alone takes all candidates (one slab) when there are at
+// least two blocks per slot; fewer blocks (few queries, e.g. the items x users side of Netflix) split the candidates into
+// slabs until there are, but no slab below kTopkMinSlab candidates.  The result does not depend on the cut.
+struct TopkCut {
+  int nslab;
+  long long slab_len;
+  long long n_items;
+  long long grid;
+};
+TopkCut topk_cut(long long rows, long long ncand, int cus, int wgs_per_cu) {
+  const long long qblocks = (rows + kTopkQB - 1) / kTopkQB;
+  const long long slots = (long long)cus * wgs_per_cu;
+  long long nslab = 1;
+  if (qblocks < 2 * slots) nslab = (2 * slots + qblocks - 1) / qblocks;
+  nslab = std::min(nslab, std::max(1LL, (ncand + kTopkMinSlab - 1) / kTopkMinSlab));
+  long long slab_len = (ncand + nslab - 1) / nslab;
+  slab_len = std::max((long long)kTopkNC, (slab_len + kTopkNC - 1) / kTopkNC * kTopkNC);
+  nslab = std::max(1LL, (ncand + slab_len - 1) / slab_len);
+  const long long items = qblocks * nslab;
+  return TopkCut{(int)nslab, slab_len, items, std::min(items, slots)};
+}
+
+bool topk_ok(int f, int k) { return f >= 1 && f <= kTopkMaxF && k >= 1 && k <= kTopkMaxK; }
+
+template <typename T>
+int scratch(hipStream_t stream, int kind, size_t count, T** out) {
+  void* q = nullptr;
+  const int rc = scratch_get(stream, kind, (count ? count : 1) * sizeof(T), &q);
+  *out = static_cast<T*>(q);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int cumf_topk_available(int f, int k) { return topk_ok(f, k); }
+
+extern "C" int cumf_topk(const float* Q, long rows, const float* C, long ncand, int f, const void* excl_rowptr,
+                         int rowptr_is_64, const int* excl_colidx, int k, int* ids, float* scores, void* stream) {
+  if (!topk_ok(f, k) || rows < 0 || ncand < 0 || ncand > 0x7fffffffL || (rows > 0 && (!Q || !ids || !scores)) ||
+      (ncand > 0 && !C) || (!excl_rowptr) != (!excl_colidx)) {
+    fprintf(stderr,
+            "cumf_topk: needs 1 <= f <= %d (got %d), 1 <= k <= %d (got %d), rows >= 0, 0 <= ncand < 2^31, the tables and "
+            "outputs, and both exclusion arrays or neither\n",
+            kTopkMaxF, f, kTopkMaxK, k);
+    return (int)hipErrorInvalidValue;
+  }
+  if (rows == 0) return 0;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  int dev = 0, cus = 0;
+  CUMF_HIP_CHECK(hipGetDevice(&dev));
+  CUMF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const TopkCut cut = topk_cut(rows, ncand, std::max(cus, 1), topk_score_occupancy(f > kTopkJC));
+  ScratchLease lease;
+  TopkArgs a{};
+  a.Q = Q;
+  a.rows = rows;
+  a.C = C;
+  a.ncand = ncand;
+  a.f = f;
+  a.k = k;
+  a.excl_rowptr = excl_rowptr;
+  a.rowptr64 = rowptr_is_64 ? 1 : 0;
+  a.excl_colidx = excl_colidx;
+  a.vec = (f % 4 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
+  a.nslab = cut.nslab;
+  a.slab_len = cut.slab_len;
+  a.n_items = cut.n_items;
+  a.ids = ids;
+  a.scores = scores;
+  int rc = scratch(s, kScratchTopkWork, (size_t)cut.grid * kTopkQB * (k + kTopkBuf), &a.work);
+  if (!rc && cut.nslab > 1) rc = scratch(s, kScratchTopkPart, (size_t)cut.nslab * rows * k, &a.part);
+  if (rc) return rc;
+  CUMF_HIP_CHECK(launch_topk_score(a, cut.grid, s));
+  if (cut.nslab > 1) CUMF_HIP_CHECK(launch_topk_merge(a.part, rows, k, cut.nslab, ids, scores, s));
+  return 0;
+}
+
+extern "C" int cumf_ranking_metrics(const int* ids, long rows, int k, const void* test_rowptr, int rowptr_is_64,
+                                    const int* test_colidx, const float* test_val, double* out4_f64, void* stream) {
+  if (k < 1 || rows < 0 || !out4_f64 || (rows > 0 && (!ids || !test_rowptr || !test_colidx))) {
+    fprintf(stderr, "cumf_ranking_metrics: needs k >= 1 (got %d), rows >= 0, ids, the held-out CSR and out4_f64\n", k);
+    return (int)hipErrorInvalidValue;
+  }
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchLease lease;
+  double* part = nullptr;
+  int rc = scratch(s, kScratchTopkMetrics, (size_t)4 * rows, &part);
+  if (rc) return rc;
+  CUMF_HIP_CHECK(launch_topk_metrics(ids, rows, k, test_rowptr, rowptr_is_64 ? 1 : 0, test_colidx, test_val, part, out4_f64, s));
+  return 0;
+}

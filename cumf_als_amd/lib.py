@@ -1,5 +1,5 @@
-"""ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h, cumf_dist_capi.h and
-cumf_implicit_capi.h).
+"""ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h, cumf_dist_capi.h,
+cumf_implicit_capi.h and cumf_topk_capi.h).
 
 The library is the product: there is no Python or CPU fallback.  `load()` raises
 when the shared object is missing or lacks a declared symbol.
@@ -37,6 +37,8 @@ IMPLICIT_SYMBOLS = [
     "cumf_implicit_available", "cumf_implicit_gram", "cumf_get_hermitian_implicit", "cumf_als_update_implicit",
     "cumf_implicit_loss",
 ]
+# every extern "C" symbol declared in include/cumf_topk_capi.h (top-k recommendation and ranking metrics, als_topk.cpp)
+TOPK_SYMBOLS = ["cumf_topk_available", "cumf_topk", "cumf_ranking_metrics"]
 # C++-linkage drop-in symbols (include/als.h, include/cg.h) under the reference's mangled names
 CXX_SYMBOLS = [
     "_Z5doALSPKiS0_PKfS0_S0_S2_S0_PfS3_S0_S0_S2_iiillfiiii",
@@ -66,7 +68,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  cumf_als_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + TOPK_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols declared in include/: {missing}")
 
@@ -189,6 +191,13 @@ def load():
     lib.cumf_implicit_loss.restype = C.c_int
     lib.cumf_implicit_loss.argtypes = [ip, ip, fp, fp, fp, C.c_long, C.c_long, C.c_int, C.c_float, C.c_float, C.c_int, vp,
                                        vp]
+    # include/cumf_topk_capi.h
+    lib.cumf_topk_available.restype = C.c_int
+    lib.cumf_topk_available.argtypes = [C.c_int, C.c_int]
+    lib.cumf_topk.restype = C.c_int
+    lib.cumf_topk.argtypes = [fp, C.c_long, fp, C.c_long, C.c_int, vp, C.c_int, ip, C.c_int, ip, fp, vp]
+    lib.cumf_ranking_metrics.restype = C.c_int
+    lib.cumf_ranking_metrics.argtypes = [ip, C.c_long, C.c_int, vp, C.c_int, ip, fp, vp, vp]
     host_args = [vp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_float, C.c_int, C.c_int, C.c_int,
                              C.c_int]
     lib.cumf_doALS.restype = C.c_float
