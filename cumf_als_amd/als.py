@@ -10,6 +10,8 @@
 * `ImplicitALSEngine` does the same for implicit feedback (include/cumf_implicit_capi.h): the
   confidence-weighted model of Hu, Koren and Volinsky, over `implicit_gram`, `update_implicit`,
   `implicit_loss`.
+* `nnls_solve`, `update_nonneg`, `update_implicit_nonneg` (include/cumf_nnls_capi.h): non-negative least squares on
+  materialised systems by block principal pivoting; both engines take `nonnegative=True` to keep every factor >= 0.
 * `topk`, `ranking_metrics` (include/cumf_topk_capi.h): the k best candidates per query, scored by a fused HIP kernel
   that never writes the score matrix, and precision / recall / NDCG@k against held-out entries; both engines expose them
   as `recommend(k, side)` and `ranking_metrics(k, side)`.
@@ -461,6 +463,73 @@ def release_scratch() -> None:
 
 
 # ---------------------------------------------------------------------------------------
+# non-negative least squares and non-negative ALS (include/cumf_nnls_capi.h)
+# ---------------------------------------------------------------------------------------
+
+NNLS_MAX_F = 128
+
+
+def nnls_available(f: int) -> bool:
+    """Does nnls_solve take f (1 <= f <= 128)?"""
+    return bool(_libmod.load().cumf_nnls_available(int(f)))
+
+
+def _check_nonneg_f(f: int) -> None:
+    if not (8 <= int(f) <= NNLS_MAX_F and int(f) % 2 == 0):
+        raise ValueError(f"non-negative ALS takes even 8 <= f <= {NNLS_MAX_F} (got f = {f})")
+
+
+def _nnls_stats(stats):
+    import torch
+
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < 2):
+        raise TypeError("stats must be an int64 tensor of 2 entries on the device")
+    return _dp(stats, torch.int64)
+
+
+def nnls_solve(A, b, x, max_iters: int = 0, stats=None):
+    """x = argmin_{x >= 0} 1/2 x^T A x - b^T x for each system of the batch (cumf_nnls_solve_batched): A batch x f x f
+    (SPD, both triangles), b and x batch x f, fp32 on the device.  x is the warm start (passive set {x > 0}) and receives
+    the solution; A and b are not modified.  max_iters: passive-set steps per system, 0 = the library default.  stats: an
+    optional int64 tensor [2] that is ADDED to: (systems not converged, factorisations)."""
+    import torch
+
+    f = b.shape[-1]
+    batch = b.numel() // f if f else 0
+    _libmod.check(_libmod.load().cumf_nnls_solve_batched(
+        _dp(A, torch.float32), _dp(b, torch.float32), _dp(x, torch.float32), batch, int(f), int(max_iters),
+        _nnls_stats(stats), _stream()), "cumf_nnls_solve_batched")
+    return x
+
+
+def update_nonneg(plan: Plan, colidx, val, gather, update, lambda_: float, max_iters: int = 0, stats=None):
+    """One explicit non-negative half-iteration over the plan's rows (cumf_als_update_nonneg): the systems of
+    `get_hermitian` solved by `nnls_solve` with `update` as warm start and output; rows without ratings get 0."""
+    import torch
+
+    lib = _libmod.load()
+    _libmod.check(lib.cumf_check_gather_table(gather.shape[0], plan.f, SOLVER_LU, 1), "cumf_check_gather_table")
+    _libmod.check(lib.cumf_als_update_nonneg(plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32),
+                                             _dp(gather, torch.float32), _dp(update, torch.float32), plan.f,
+                                             float(lambda_), int(max_iters), _nnls_stats(stats), _stream()),
+                  "cumf_als_update_nonneg")
+    return update
+
+
+def update_implicit_nonneg(plan: Plan, colidx, val, gather, G, update, lambda_: float, alpha: float, reg="weighted",
+                           max_iters: int = 0, stats=None):
+    """One implicit non-negative half-iteration (cumf_als_update_implicit_nonneg): the systems of
+    `get_hermitian_implicit` solved by `nnls_solve`; G is implicit_gram(gather); rows without entries get 0."""
+    import torch
+
+    _libmod.check(_libmod.load().cumf_als_update_implicit_nonneg(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(gather, torch.float32), _dp(G, torch.float32),
+        _dp(update, torch.float32), plan.f, float(lambda_), float(alpha), _reg_id(reg), int(max_iters),
+        _nnls_stats(stats), _stream()), "cumf_als_update_implicit_nonneg")
+    return update
+
+
+# ---------------------------------------------------------------------------------------
 # top-k recommendation and ranking metrics (include/cumf_topk_capi.h)
 # ---------------------------------------------------------------------------------------
 
@@ -562,13 +631,19 @@ class ALSEngine(_Recommender):
     """
 
     def __init__(self, r, f: int, lambda_: float, solver="cg", cg_iters: int = 6, x_batch: int = 1,
-                 theta_batch: int = 1, fused: bool = True, chunk: int = 0):
+                 theta_batch: int = 1, fused: bool = True, chunk: int = 0, nonnegative: bool = False):
         import torch
 
         self.r, self.f, self.lam = r, f, float(lambda_)
         self.solver, self.cg_iters = solver, cg_iters
+        # nonnegative: every half-iteration is update_nonneg (materialise + NNLS); solver, cg_iters and fused are unused
+        self.nonnegative = bool(nonnegative)
+        if self.nonnegative:
+            _check_nonneg_f(f)
+            self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
         # above the tile kernels' range (f > 207) the reference's unfused data flow runs (cumf_get_hermitian + batched solver)
-        self.fused = bool(fused) and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver)))
+        self.fused = (not self.nonnegative and bool(fused)
+                      and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver))))
         self.m, self.n = r.m, r.n
         self.device = r.csr_indices.device
         self.x_plans = self._plans(r.csr_indptr, r.m, x_batch, chunk)
@@ -604,7 +679,9 @@ class ALSEngine(_Recommender):
         import torch
 
         for p in plans:
-            if self.fused:
+            if self.nonnegative:
+                update_nonneg(p, colidx, val, gather, update, self.lam, stats=self.nnls_stats)
+            elif self.fused:
                 update_fused(p, colidx, val, gather, update, self.lam, self.solver, self.cg_iters)
             else:
                 rows = p.batch_rows
@@ -749,10 +826,15 @@ class ImplicitALSEngine(_Recommender):
     reg "weighted" (lambda n_u, the default) or "plain" (lambda)."""
 
     def __init__(self, r, f: int, lambda_: float, alpha: float, solver="cg", cg_iters: int = 3, reg="weighted",
-                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0):
+                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, nonnegative: bool = False):
         import torch
 
-        if not implicit_available(f, solver):
+        # nonnegative: every half-iteration is update_implicit_nonneg (materialise + NNLS); solver and cg_iters are unused
+        self.nonnegative = bool(nonnegative)
+        if self.nonnegative:
+            _check_nonneg_f(f)
+            self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
+        elif not implicit_available(f, solver):
             raise ValueError(f"implicit ALS takes even 8 <= f <= 128 and solver cg | lu (got f = {f}, {solver!r})")
         self.r, self.f, self.lam, self.alpha = r, f, float(lambda_), float(alpha)
         self.solver, self.cg_iters, self.reg = solver, int(cg_iters), _reg_id(reg)
@@ -771,8 +853,12 @@ class ImplicitALSEngine(_Recommender):
     def _half(self, plans, colidx, val, gather, update):
         implicit_gram(gather, self.G)
         for p in plans:
-            update_implicit(p, colidx, val, gather, self.G, update, self.lam, self.alpha, self.reg, self.solver,
-                            self.cg_iters)
+            if self.nonnegative:
+                update_implicit_nonneg(p, colidx, val, gather, self.G, update, self.lam, self.alpha, self.reg,
+                                       stats=self.nnls_stats)
+            else:
+                update_implicit(p, colidx, val, gather, self.G, update, self.lam, self.alpha, self.reg, self.solver,
+                                self.cg_iters)
 
     def update_x(self):
         self._half(self.x_plans, self.r.csr_indices, self.r.csr_data, self.thetaT, self.XT)

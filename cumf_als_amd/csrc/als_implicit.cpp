@@ -153,6 +153,15 @@ ImplicitRoute implicit_route(const cumf_plan* p, int solver) {
 
 }  // namespace
 
+int cumf::plan_empty_rows(cumf_plan* p, const int** rows, long* count) {
+  ImplicitLists* l = nullptr;
+  const int rc = implicit_lists(p, &l);
+  if (rc) return rc;
+  *rows = l->d_empty_row;
+  *count = l->n_empty;
+  return 0;
+}
+
 extern "C" int cumf_implicit_available(int f, int solver) {
   return implicit_f_ok(f) && (solver == CUMF_SOLVER_CG || solver == CUMF_SOLVER_LU);
 }

@@ -292,6 +292,9 @@ enum {
   kScratchTopkWork = 9,
   kScratchTopkPart = 10,
   kScratchTopkMetrics = 11,
+  // non-negative ALS (als_nnls.cpp): materialised systems, right-hand sides
+  kScratchNnlsTT = 12,
+  kScratchNnlsRhs = 13,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 struct ScratchLease {
@@ -388,6 +391,15 @@ hipError_t launch_topk_merge(const unsigned long long* part, long long rows, int
 hipError_t launch_topk_metrics(const int* ids, long long rows, int k, const void* rowptr, int rowptr64, const int* colidx,
                                const float* val, double* part, double* out, hipStream_t stream);
 
+// ---- Non-negative least squares (als_nnls.hip kernel, als_nnls.cpp host side; include/cumf_nnls_capi.h)
+constexpr int kNnlsMaxF = 128;
+constexpr int kNnlsMaxNB = nb_for_f(kNnlsMaxF);  // 9
+constexpr int kNnlsGrid = 2048;                  // workgroups of the grid-stride launch
+constexpr int kNnlsDefaultItersBase = 16;        // max_iters = 0: 16 + 2 f steps per system
+// cap: passive-set steps per system; stats (may be null): [0] += systems not converged, [1] += factorisations
+hipError_t launch_nnls(const float* A, const float* b, float* x, long batch, int f, int cap, long long* stats,
+                       hipStream_t stream);
+
 }  // namespace cumf
 
 // A half-iteration plan (cumf_plan_create, als_plan.cpp).
@@ -423,6 +435,10 @@ struct cumf_plan {
 };
 
 namespace cumf {
+
+// The plan's rows without stored entries (absolute row ids, device array) from the lists of als_implicit.cpp, built on
+// first use.
+int plan_empty_rows(cumf_plan* p, const int** rows, long* count);
 
 // One launch: the dynamic-LDS opt-in above 64 KB, the launch, its error.  launch_item_kernel (NOTE): a Gram(+solve)
 // kernel, also recorded for cumf_last_kernel_name.

@@ -39,6 +39,9 @@ IMPLICIT_SYMBOLS = [
 ]
 # every extern "C" symbol declared in include/cumf_topk_capi.h (top-k recommendation and ranking metrics, als_topk.cpp)
 TOPK_SYMBOLS = ["cumf_topk_available", "cumf_topk", "cumf_ranking_metrics"]
+# every extern "C" symbol declared in include/cumf_nnls_capi.h (non-negative ALS, als_nnls.cpp)
+NNLS_SYMBOLS = ["cumf_nnls_available", "cumf_nnls_solve_batched", "cumf_als_update_nonneg",
+                "cumf_als_update_implicit_nonneg"]
 # C++-linkage drop-in symbols (include/als.h, include/cg.h) under the reference's mangled names
 CXX_SYMBOLS = [
     "_Z5doALSPKiS0_PKfS0_S0_S2_S0_PfS3_S0_S0_S2_iiillfiiii",
@@ -68,7 +71,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  cumf_als_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + TOPK_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + TOPK_SYMBOLS + NNLS_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols declared in include/: {missing}")
 
@@ -198,6 +201,16 @@ def load():
     lib.cumf_topk.argtypes = [fp, C.c_long, fp, C.c_long, C.c_int, vp, C.c_int, ip, C.c_int, ip, fp, vp]
     lib.cumf_ranking_metrics.restype = C.c_int
     lib.cumf_ranking_metrics.argtypes = [ip, C.c_long, C.c_int, vp, C.c_int, ip, fp, vp, vp]
+    # include/cumf_nnls_capi.h
+    lib.cumf_nnls_available.restype = C.c_int
+    lib.cumf_nnls_available.argtypes = [C.c_int]
+    lib.cumf_nnls_solve_batched.restype = C.c_int
+    lib.cumf_nnls_solve_batched.argtypes = [fp, fp, fp, C.c_long, C.c_int, C.c_int, vp, vp]
+    lib.cumf_als_update_nonneg.restype = C.c_int
+    lib.cumf_als_update_nonneg.argtypes = [vp, ip, fp, fp, fp, C.c_int, C.c_float, C.c_int, vp, vp]
+    lib.cumf_als_update_implicit_nonneg.restype = C.c_int
+    lib.cumf_als_update_implicit_nonneg.argtypes = [vp, ip, fp, fp, fp, fp, C.c_int, C.c_float, C.c_float, C.c_int,
+                                                    C.c_int, vp, vp]
     host_args = [vp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_float, C.c_int, C.c_int, C.c_int,
                              C.c_int]
     lib.cumf_doALS.restype = C.c_float
