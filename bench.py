@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- ratings/sec per ALS half-iteration on synthetic Netflix-shaped ratings.
 
-  python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run)
 
 A "step" is one full pass of the hot path over the dataset: update-X + update-Theta
 (RHS + Gram + solve for every row of both sides), i.e. TWO half-iterations.  Inputs are
 resident in HBM before the timed region.  Workload = BASELINE.json configs[1]:
 Netflix shape (17770 x 480189, 99 072 112 ratings), f = 100, lambda = 0.048, LU solver.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line with the headline figure
+(N > 1: also the native half-iterations, which take the line over when faster).  --full adds everything else
+below: N = 1 the roofline leg, the RMSE, the other gram modes, cpu_baseline and parity_at_scale; N > 1 the per-rank
+diagnostics and the hugewiki leg.
+
 Printed JSON (one line, rank 0):
   value       2 * nnz * K / t           ratings/s per half-iteration, whole job
-  roofline    dominant kernel = the per-item Gram(+solve) launch that takes the larger part of the step (the
+  dtype       the arithmetic of the X-side Gram(+solve) kernel
+  roofline    (--full) dominant kernel = the per-item Gram(+solve) launch that takes the larger part of the step (the
               Theta-side instance at the headline shape; its name is read back from the library: the symbol
               that was dispatched); achieved = algorithmic bytes of that half-iteration (SURVEY.md 8d:
               4 f nnz + 8 nnz + 4 (rows+1) + 4 f rows) / its HIP-event duration; peak = 8 TB/s HBM.  Both
@@ -18,7 +24,7 @@ Printed JSON (one line, rank 0):
               for every --f, --solver and for --shape hugewiki (per-GPU slab).  `traffic` is replayed
               from the committed rocprofv3 --pmc passes (profiles/traffic.json), and only when that file
               was collected for the kernel that was dispatched here.
-  cpu_baseline  the CPU oracle (oracle/, "port": the reference has no CPU path) timed on
+  cpu_baseline  (--full) the CPU oracle (oracle/, "port": the reference has no CPU path) timed on
               this host's cores on a row sample of the same matrix, N = 1 only.
 
 --dump-outputs DIR writes what the last timed step computed -- the factors X (x.npy) and Theta (theta.npy) -- after the
@@ -52,6 +58,15 @@ def alg_bytes(nnz: int, rows: int, f: int, cg: bool) -> float:
     if cg:
         b += 4.0 * f * rows
     return b
+
+
+def kernel_dtype(kernel: str, mode: str) -> str:
+    """The line's dtype: the arithmetic of the Gram(+solve) kernel `kernel` (a cumf_last_kernel_name) in gram mode `mode`."""
+    if "als_wave" not in kernel:
+        return "f32"
+    if mode == "fast":
+        return "f32 (opt-in fast mode: pre-split f16x2 operands, 3 products, 22-bit significand, fp32 accumulate)"
+    return "f32 (bf16x3-split products on the bf16 matrix pipe, fp32 accumulate)"
 
 
 DUMP_BYTES = 64_000_000  # --dump-outputs: all files together, headers included
@@ -693,6 +708,10 @@ def main() -> int:
     ap.add_argument("--scheme", default="gather", choices=["gather", "reduce"])
     ap.add_argument("--theta-batch", type=int, default=0,
                     help="--shape hugewiki: Theta batches of the reduce scheme (0 = 3 when more than one rank, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: N = 1 the roofline leg, the RMSE, the other gram modes, "
+                         "the CPU baseline and the parity legs; N > 1 the per-rank diagnostics and the hugewiki leg "
+                         "(the --no-* options below pick among them)")
     ap.add_argument("--no-fast-leg", action="store_true",
                     help="skip the informational legs in the other gram modes (opt-in fast, reference-exact)")
     ap.add_argument("--allow-missing-traffic", action="store_true",
@@ -863,8 +882,8 @@ def main() -> int:
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, {"x": eng.XT, "theta": eng.thetaT})
 
-    diag = None
-    if world > 1:
+    diag = {}
+    if world > 1 and a.full:
         diag = rank_diagnostics(eng, als, dev, world, backend)
     out = None
     if rank == 0:
@@ -889,15 +908,17 @@ def main() -> int:
         out["ranks"] = {"n_ranks_seen": dist.get_world_size(), "backend": backend,
                         "devices_visible": torch.cuda.device_count(),
                         "scheme": "reduce" if slab_mode else a.scheme,
-                        "self_launched": os.environ.get("CUMF_BENCH_SELF_LAUNCHED") == "1",
-                        "note": "half_ms = compute-stream time of a half-iteration (ranks aligned by a barrier first); "
-                                "kernel_ms = libALS Gram(+solve) launches inside it (HIP events, summed); non_kernel_ms = "
-                                "exposed collectives + waiting for the slowest rank + launch gaps"
-                                + (" + the batched solve / unpack kernels of the reduce scheme" if slab_mode or a.scheme == "reduce" else ""),
-                        **diag}
+                        "self_launched": os.environ.get("CUMF_BENCH_SELF_LAUNCHED") == "1"}
+        if diag:
+            out["ranks"].update(
+                note="half_ms = compute-stream time of a half-iteration (ranks aligned by a barrier first); "
+                     "kernel_ms = libALS Gram(+solve) launches inside it (HIP events, summed); non_kernel_ms = "
+                     "exposed collectives + waiting for the slowest rank + launch gaps"
+                     + (" + the batched solve / unpack kernels of the reduce scheme" if slab_mode or a.scheme == "reduce" else ""),
+                **diag)
     if world > 1:
-        # The Netflix line is complete here.  The hugewiki leg (the configuration the 8-GPU target is defined on) runs behind
-        # it under a guard that prints the line -- with hugewiki: {"error": ...} -- if the leg hangs or the launcher tears
+        # The Netflix line is complete here.  The hugewiki leg (--full: the configuration the 8-GPU target is defined on) runs
+        # behind it under a guard that prints the line -- with hugewiki: {"error": ...} -- if the leg hangs or the launcher tears
         # the job down; a failure inside the leg comes back as the same object (every rank: the leg holds collectives).
         guard = LineGuard(out, float(os.environ.get("CUMF_BENCH_LEG_DEADLINE", "600")))
         if not slab_mode and not a.no_native_leg:
@@ -909,28 +930,31 @@ def main() -> int:
 
             def measure(e):
                 elapsed_n = timed_steps(e, dev, backend, a.steps, a.warmup)
-                d = rank_diagnostics(e, als, dev, world, backend)
-                return {"value": 2.0 * nnz * a.steps / elapsed_n, "ms_per_step": 1e3 * elapsed_n / a.steps,
-                        "ranks": {"per_rank": d["per_rank"], "max_over_ranks": d["max_over_ranks"],
-                                  "steps_averaged": d["steps_averaged"]}}
+                res = {"value": 2.0 * nnz * a.steps / elapsed_n, "ms_per_step": 1e3 * elapsed_n / a.steps}
+                if a.full:
+                    d = rank_diagnostics(e, als, dev, world, backend)
+                    res["ranks"] = {k: d[k] for k in ("per_rank", "max_over_ranks", "steps_averaged")}
+                return res
 
             nat = native_leg(make_engine, measure, theta0, factors_t, dev, world, rank, backend)
 
             def take_over(line):
                 if "error" not in nat and nat["ms_per_step"] <= 1.02 * line["ms_per_step"]:
                     # rank 0's line: the diagnostics of the path whose numbers it carries
-                    ranks_t = {k: line["ranks"].pop(k) for k in ("per_rank", "max_over_ranks", "steps_averaged")}
-                    line["ranks"].update(nat.pop("ranks"))
+                    ranks_t = ({k: line["ranks"].pop(k) for k in ("per_rank", "max_over_ranks", "steps_averaged")}
+                               if a.full else None)
+                    line["ranks"].update(nat.pop("ranks", {}))
                     line["ranks"]["transport"] = nat.pop("transport")
                     promote_native(line, nat, ("value", "ms_per_step"))
-                    line["torch_collectives"]["ranks"] = ranks_t
+                    if ranks_t is not None:
+                        line["torch_collectives"]["ranks"] = ranks_t
                 else:
                     promote_native(line, nat, ())
 
             guard.note(take_over)
             del factors_t
         hw = None
-        if not slab_mode and not a.no_hugewiki_leg:
+        if a.full and not slab_mode and not a.no_hugewiki_leg:
             guard.pending = ("hugewiki",)
             close = getattr(eng, "close", None)
             if close is not None:
@@ -943,6 +967,14 @@ def main() -> int:
             dist.destroy_process_group()
         except Exception:  # noqa: BLE001 -- the line is out; a failed teardown must not turn the run into an error
             pass
+        return 0
+    if not a.full:
+        # dtype names the arithmetic of the X-side kernel, which the roofline leg reads under --full; here one X
+        # half-iteration behind the timed steps and the dump names it
+        eng.update_x()
+        torch.cuda.synchronize()
+        out["dtype"] = kernel_dtype(als.last_kernel_name(), als.get_gram_mode())
+        print(json.dumps(out), flush=True)
         return 0
     if world == 1:
         # roofline leg: the same steps again with HIP events around each kernel launch
@@ -1007,9 +1039,7 @@ def main() -> int:
         gram_only = None
         if wave and not slab_mode and not a.no_gram_leg:
             gram_only = gram_pass_alone(a)
-        out["dtype"] = ("f32" if not wave else
-                        "f32 (opt-in fast mode: pre-split f16x2 operands, 3 products, 22-bit significand, fp32 accumulate)"
-                        if mode == "fast" else "f32 (bf16x3-split products on the bf16 matrix pipe, fp32 accumulate)")
+        out["dtype"] = kernel_dtype(kernel, mode)
         sx_, st_ = side(xs, bx, "x_side", kernels.get("x")), side(ts, bt, "theta_side", kernels.get("theta"))
         dom_name, dom = ("theta_side", st_) if ts >= xs else ("x_side", sx_)
         out["roofline"] = {

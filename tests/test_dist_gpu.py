@@ -273,7 +273,7 @@ def test_bench_world2_branch_runs(alslib, args, launch):
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py")]
-    cmd += ["--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--no-cpu-baseline"] + args
+    cmd += ["--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--full", "--no-cpu-baseline"] + args
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -316,6 +316,40 @@ def test_bench_world2_branch_runs(alslib, args, launch):
         assert len(hw["per_rank"]["x_half_ms"]) == 2 and "configs[3]" in hw["workload"]
 
 
+def test_bench_world2_plain_line(alslib):
+    """Without --full the N > 1 line carries the headline alone: measured on torch.distributed collectives and taken over by
+    the native half-iterations when they measure faster, with neither the per-rank diagnostics nor the hugewiki leg."""
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU")
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from tests.test_dist_cpu import _free_port
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CUMF_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--scheme", "gather"]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["value"] > 0 and np.isfinite(line["value"]) and line["ms_per_step"] > 0
+    assert line["ranks"]["n_ranks_seen"] == 2
+    assert "hugewiki" not in line and "per_rank" not in line["ranks"], line
+    assert line["native_equals_torch_collectives"] is True, line
+    if line["collectives"].startswith("native"):
+        assert line["ranks"]["transport"] == "custom" and line["torch_collectives"]["ms_per_step"] > 0
+        assert "ranks" not in line["torch_collectives"], line
+    else:
+        assert line["native"]["ms_per_step"] > 1.02 * line["ms_per_step"]
+
+
 @pytest.mark.parametrize("fault", ["rank1_raises", "hang"])
 def test_bench_line_survives_a_failing_hugewiki_leg(alslib, fault):
     """the driver gets one shot at N = 8, and the hugewiki leg runs behind the Netflix line in
@@ -340,7 +374,8 @@ def test_bench_line_survives_a_failing_hugewiki_leg(alslib, fault):
                CUMF_BENCH_FAIL_LEG="1" if fault == "rank1_raises" else "hang1", CUMF_BENCH_LEG_DEADLINE="20")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--no-cpu-baseline", "--scheme", "gather"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--full", "--no-cpu-baseline", "--scheme",
+           "gather"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (out.stdout[-2000:], out.stderr[-2000:])
@@ -373,7 +408,8 @@ def test_bench_line_survives_a_failing_native_leg(alslib, fault):
                CUMF_BENCH_FAIL_NATIVE="1" if fault == "rank1_raises" else "hang1", CUMF_BENCH_LEG_DEADLINE="60")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--no-cpu-baseline", "--scheme", "gather"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--scale", "0.05", "--full", "--no-cpu-baseline", "--scheme",
+           "gather"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (out.stdout[-2000:], out.stderr[-2000:])

@@ -347,6 +347,40 @@ def test_dispatched_kernel_name_and_committed_traffic(alslib):
         als.set_debug_switches(1)
 
 
+def test_bench_plain_line_and_full_legs(alslib, tmp_path):
+    """bench.py without --full prints the headline line alone -- the same keys, dtype and dumped factors as a --full run of
+    the same steps -- and --full adds the roofline, RMSE, gram-mode, CPU-baseline and parity legs behind them."""
+    _need_gpu()
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = {}, {}
+    for tag, extra in (("plain", []), ("full", ["--full"])):
+        out_dir = str(tmp_path / tag)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--scale", "0.05", "--dump-outputs", out_dir] + extra
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        got = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1, out.stdout[-2000:]
+        lines[tag] = json.loads(got[0])
+        dumps[tag] = {k: np.load(os.path.join(out_dir, k + ".npy")) for k in ("x", "theta")}
+    plain, full = lines["plain"], lines["full"]
+    legs = {"roofline", "rmse", "gram_fast_mode", "gram_exact_mode", "cpu_baseline", "parity_at_scale"}
+    assert legs <= set(full), sorted(full)
+    assert set(plain) == set(full) - legs, sorted(plain)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert plain[k] == full[k], (k, plain[k], full[k])
+    assert plain["config"]["workload"] == full["config"]["workload"]
+    assert plain["dtype"] == "f32 (bf16x3-split products on the bf16 matrix pipe, fp32 accumulate)", plain["dtype"]
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    for k in ("x", "theta"):  # the timed steps and what they leave behind do not depend on --full
+        assert np.array_equal(dumps["plain"][k], dumps["full"][k], equal_nan=True), k
+
+
 def test_whole_row_kernel_is_bit_identical_to_the_combined_one(alslib):
     """The LU wave kernel has two instances: WHOLE (the plan has no chunked row: no partial-tile exit, 0 spills) and
     the combined one (a plan whose chunked rows hold a quarter or more of its ratings: one launch, the whole rows fill the

@@ -3,7 +3,7 @@
 # e.g. tools/ab_env.sh "--f 100 --solver lu" "CUMF_ALS_PRESPLIT=0" "CUMF_ALS_PRESPLIT=-" 3   ("X=-" leaves X unset)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 ARGS="$1"; A="$2"; B="$3"; N=${4:-3}; S=${5:-30}; W=${6:-10}
-Q="--no-cpu-baseline --no-fast-leg --no-gram-leg --allow-missing-traffic --steps $S --warmup $W"
+Q="--full --no-cpu-baseline --no-fast-leg --no-gram-leg --allow-missing-traffic --steps $S --warmup $W"
 for i in $(seq $N); do
   for E in "$A" "$B"; do
     K=${E%%=*}; V=${E#*=}

@@ -1,5 +1,5 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-Q="--no-cpu-baseline --no-fast-leg --no-gram-leg --allow-missing-traffic --steps 10 --warmup 2 --no-rmse-log"
+Q="--full --no-cpu-baseline --no-fast-leg --no-gram-leg --allow-missing-traffic --steps 10 --warmup 2 --no-rmse-log"
 ARGS="$1"; shift
 N=$1; shift
 for i in $(seq $N); do

@@ -20,7 +20,7 @@ if [ "${GRAM_ONLY:-0}" = "1" ]; then
   export CUMF_ALS_LIB=$R/cumf_als_amd/csrc/libALS_ablate.so
   BENCH="python $R/tools/gram_pass_alone.py ${BENCH_ARGS:-}"
 else
-  BENCH="python $R/bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-gram-leg --no-fast-leg --allow-missing-traffic ${BENCH_ARGS:-}"
+  BENCH="python $R/bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-gram-leg --no-fast-leg --allow-missing-traffic ${BENCH_ARGS:-}"
 fi
 echo "$BENCH" > $OUT/command.txt
 rm -rf /tmp/prof_kt /tmp/prof_sq /tmp/prof_f /tmp/prof_w /tmp/prof_t

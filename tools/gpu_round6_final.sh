@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 O=$R/gpurun_out/r06final; mkdir -p $O $R/gpurun_out/r06
-timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
 export ROUND=r06
 TAG=lu FULL=1 BENCH_ARGS="--solver lu" timeout 500 tools/collect_profiles.sh > /dev/null 2>&1
 TAG=cg BENCH_ARGS="--solver cg" timeout 400 tools/collect_profiles.sh > /dev/null 2>&1
@@ -20,8 +20,8 @@ rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INS
 python $R/tools/pmc_summary.py /tmp/prof_x > $R/gpurun_out/profiles_r06/lu/pmc_lds.txt
 cd $R
 tools/gpu_round6_sweep.sh final > /dev/null 2>&1; cp $R/gpurun_out/r06/sweep_final.txt $O/final_sweep.txt; cat $O/final_sweep.txt
-CUMF_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err; echo "2-rank bench rc=$?"
-CUMF_BENCH_BACKEND=gloo timeout 1200 python bench.py --gpus 8 --steps 2 --warmup 1 --scale 0.1 --no-cpu-baseline > $O/bench_8ranks_gloo.json 2> $O/bench_8ranks_gloo.err; echo "8-rank bench rc=$?"
+CUMF_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err; echo "2-rank bench rc=$?"
+CUMF_BENCH_BACKEND=gloo timeout 1200 python bench.py --full --gpus 8 --steps 2 --warmup 1 --scale 0.1 --no-cpu-baseline > $O/bench_8ranks_gloo.json 2> $O/bench_8ranks_gloo.err; echo "8-rank bench rc=$?"
 python -m cumf_als_amd.datagen --shape netflix /tmp/netflix_synth > /dev/null 2>&1
 cd cumf_als_amd/csrc
 for solver in lu cg; do
