@@ -746,6 +746,13 @@ class ALSEngine(_Recommender):
 # ---------------------------------------------------------------------------------------
 
 IMPLICIT_REG_WEIGHTED, IMPLICIT_REG_PLAIN = 0, 1
+SOLVER_CG_MATFREE = 2  # CUMF_SOLVER_CG_MATFREE: implicit feedback only
+
+
+def _implicit_solver_id(solver) -> int:
+    if solver in (SOLVER_CG_MATFREE, "cg_matfree"):
+        return SOLVER_CG_MATFREE
+    return _solver_id(solver)
 
 
 def _reg_id(reg) -> int:
@@ -757,7 +764,8 @@ def _reg_id(reg) -> int:
 
 
 def implicit_available(f: int, solver="cg") -> bool:
-    return bool(_libmod.load().cumf_implicit_available(int(f), _solver_id(solver)))
+    """cumf_implicit_available: "cg" / "lu" take even 8 <= f <= 128, "cg_matfree" even 8 <= f <= 512."""
+    return bool(_libmod.load().cumf_implicit_available(int(f), _implicit_solver_id(solver)))
 
 
 def implicit_gram(table, G=None):
@@ -793,12 +801,13 @@ def get_hermitian_implicit(plan: Plan, colidx, val, gather, G, lambda_: float, a
 def update_implicit(plan: Plan, colidx, val, gather, G, update, lambda_: float, alpha: float, reg="weighted", solver="cg",
                     cg_iters: int = 3):
     """One implicit half-iteration over the plan's rows (cumf_als_update_implicit); `update` is the CG warm start and
-    receives the solution, G is implicit_gram(gather)."""
+    receives the solution, G is implicit_gram(gather).  solver "cg", "lu" or "cg_matfree" (the operator-only CG)."""
     import torch
 
     _libmod.check(_libmod.load().cumf_als_update_implicit(
         plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(gather, torch.float32), _dp(G, torch.float32),
-        _dp(update, torch.float32), plan.f, float(lambda_), float(alpha), _reg_id(reg), _solver_id(solver), int(cg_iters),
+        _dp(update, torch.float32), plan.f, float(lambda_), float(alpha), _reg_id(reg), _implicit_solver_id(solver),
+        int(cg_iters),
         _stream()), "cumf_als_update_implicit")
     return update
 
@@ -822,8 +831,10 @@ class ImplicitALSEngine(_Recommender):
     """Implicit-feedback ALS on one GPU: the ratings of `r` (a `datagen.Ratings` on the device) are interaction
     strengths -- weight alpha |r|, preference r > 0 -- and every unstored entry counts as a preference of 0 with
     confidence 1.  Same shape as `ALSEngine`; each half-iteration forms G = Y^T Y of the fixed side once, before its
-    batches.  solver "cg" (warm-started, `cg_iters` steps; rows of at most 32 entries never form their system) or "lu";
-    reg "weighted" (lambda n_u, the default) or "plain" (lambda)."""
+    batches.  solver "cg" (warm-started, `cg_iters` steps; rows of at most 32 entries never form their system), "lu" or
+    "cg_matfree" (the same CG recurrence, no row ever forms its system); reg "weighted" (lambda n_u, the default) or
+    "plain" (lambda).  "cg" and "lu" take even 8 <= f <= 128, "cg_matfree" even 8 <= f <= 512; at 128 < f <= 512
+    solver "cg" runs "cg_matfree", the only CG there ("lu" and nonnegative=True stay limited to f <= 128)."""
 
     def __init__(self, r, f: int, lambda_: float, alpha: float, solver="cg", cg_iters: int = 3, reg="weighted",
                  x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, nonnegative: bool = False):
@@ -834,8 +845,12 @@ class ImplicitALSEngine(_Recommender):
         if self.nonnegative:
             _check_nonneg_f(f)
             self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
-        elif not implicit_available(f, solver):
-            raise ValueError(f"implicit ALS takes even 8 <= f <= 128 and solver cg | lu (got f = {f}, {solver!r})")
+        else:
+            if solver in (SOLVER_CG, "cg", "CG") and 128 < f <= 512:
+                solver = "cg_matfree"  # the only CG above f = 128
+            if not implicit_available(f, solver):
+                raise ValueError(f"implicit ALS takes even 8 <= f <= 128 with solver cg | lu and even 8 <= f <= 512 with "
+                                 f"cg | cg_matfree (got f = {f}, {solver!r})")
         self.r, self.f, self.lam, self.alpha = r, f, float(lambda_), float(alpha)
         self.solver, self.cg_iters, self.reg = solver, int(cg_iters), _reg_id(reg)
         self.m, self.n = r.m, r.n

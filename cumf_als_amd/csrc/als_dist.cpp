@@ -292,7 +292,7 @@ extern "C" int cumf_dist_gather_create(cumf_dist_gather_t** out, cumf_comm_t* co
 extern "C" int cumf_dist_gather_update(cumf_dist_gather_t* s, const cumf_plan_t* const* piece_plans, const int* colidx,
                                        const float* val, const float* table, float* out, float lambda, int solver,
                                        int cg_iters, double* sse_bins, void* stream) {
-  if (!s || !piece_plans || !out) return (int)hipErrorInvalidValue;
+  if (!s || !piece_plans || !out || (solver != CUMF_SOLVER_CG && solver != CUMF_SOLVER_LU)) return (int)hipErrorInvalidValue;
   cumf_comm* c = s->comm;
   const int w = c->world, me = c->rank, f = s->f;
   hipStream_t S = static_cast<hipStream_t>(stream), C = c->comm_stream;
@@ -401,7 +401,9 @@ extern "C" int cumf_dist_reduce_update_theta(cumf_dist_reduce_t* r, const cumf_p
                                              const int* lc_rowidx, const float* lc_val, const float* XT_slab,
                                              float* thetaT, float lambda, int solver, int cg_iters,
                                              const float* reg_all, double* sse_terms, void* stream) {
-  if (!r || !batch_plans || !thetaT || (reg_all == nullptr) != (sse_terms == nullptr)) return (int)hipErrorInvalidValue;
+  if (!r || !batch_plans || !thetaT || (reg_all == nullptr) != (sse_terms == nullptr) ||
+      (solver != CUMF_SOLVER_CG && solver != CUMF_SOLVER_LU))
+    return (int)hipErrorInvalidValue;
   cumf_comm* c = r->comm;
   const int w = c->world, me = c->rank, f = r->f;
   hipStream_t S = static_cast<hipStream_t>(stream), C = c->comm_stream;

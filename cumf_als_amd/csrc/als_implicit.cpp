@@ -26,11 +26,18 @@ struct ImplicitLists {
   int* d_item_dst = nullptr;   // n_long_items: item -> compact index of its row
   int* d_mrow_dst = nullptr;   // n_mrows: chunked row -> compact index
   int* d_empty_row = nullptr;  // n_empty
+  // the matrix-free CG's segments and per-row lists (ImplicitFreeArgs), built on its first use; rows: row - row_begin
+  bool free_built = false;
+  long n_seg = 0;
+  char* d_free = nullptr;
+  long long* d_seg_begin = nullptr;
+  int *d_seg_row = nullptr, *d_seg_len = nullptr, *d_row_seg0 = nullptr, *d_row_nseg = nullptr, *d_row_len = nullptr;
 };
 
 void free_implicit_lists(ImplicitLists* l) {
   if (!l) return;
   if (l->d_block) (void)hipFree(l->d_block);
+  if (l->d_free) (void)hipFree(l->d_free);
   delete l;
 }
 
@@ -39,6 +46,12 @@ void free_implicit_lists(ImplicitLists* l) {
 namespace {
 
 bool implicit_f_ok(int f) { return f >= 8 && f <= 128 && (f % 2) == 0; }
+// the matrix-free CG, and the Gram and objective it needs
+bool matfree_f_ok(int f) { return f >= 8 && f <= 512 && (f % 2) == 0; }
+bool solver_f_ok(int f, int solver) {
+  if (solver == CUMF_SOLVER_CG_MATFREE) return matfree_f_ok(f);
+  return implicit_f_ok(f) && (solver == CUMF_SOLVER_CG || solver == CUMF_SOLVER_LU);
+}
 
 int implicit_lists(cumf_plan* p, ImplicitLists** out) {
   if (p->implicit) {
@@ -94,6 +107,57 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
   return 0;
 }
 
+// The segments of the plan's rows: a row of n entries starts where its first item does (a cut row's chunks are
+// consecutive) and is cut at the offsets 0, kFreeSeg, 2 kFreeSeg, ... from there, whatever the plan's own chunks.
+int free_lists(cumf_plan* p, ImplicitLists* l) {
+  if (l->free_built) return 0;
+  const size_t ni = (size_t)p->n_items, rows = (size_t)(p->row_end - p->row_begin);
+  std::vector<int> row(ni), rowlen(ni);
+  std::vector<long long> begin(ni);
+  if (ni) {
+    CUMF_HIP_CHECK(hipMemcpy(row.data(), p->d_item_row, ni * sizeof(int), hipMemcpyDeviceToHost));
+    CUMF_HIP_CHECK(hipMemcpy(rowlen.data(), p->d_item_rowlen, ni * sizeof(int), hipMemcpyDeviceToHost));
+    CUMF_HIP_CHECK(hipMemcpy(begin.data(), p->d_item_begin, ni * sizeof(long long), hipMemcpyDeviceToHost));
+  }
+  std::vector<long long> start(rows, -1);
+  std::vector<int> len(rows, 0);
+  for (size_t i = 0; i < ni; ++i) {
+    const size_t u = (size_t)(row[i] - p->row_begin);
+    if (start[u] < 0 || begin[i] < start[u]) start[u] = begin[i];
+    len[u] = rowlen[i];
+  }
+  std::vector<long long> seg_begin;
+  std::vector<int> seg_row, seg_len, row_seg0(rows), row_nseg(rows);
+  for (size_t u = 0; u < rows; ++u) {
+    row_seg0[u] = (int)seg_row.size();
+    for (int o = 0; o < len[u]; o += kFreeSeg) {
+      seg_begin.push_back(start[u] + o);
+      seg_row.push_back((int)u);
+      seg_len.push_back(len[u] - o < kFreeSeg ? len[u] - o : kFreeSeg);
+    }
+    row_nseg[u] = (int)seg_row.size() - row_seg0[u];
+  }
+  const size_t ns = seg_row.size();
+  std::vector<int> ints;
+  for (auto* v : {&seg_row, &seg_len, &row_seg0, &row_nseg, &len}) ints.insert(ints.end(), v->begin(), v->end());
+  const size_t bytes = ns * sizeof(long long) + ints.size() * sizeof(int);
+  if (bytes) {
+    CUMF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&l->d_free), bytes));
+    if (ns) CUMF_HIP_CHECK(hipMemcpy(l->d_free, seg_begin.data(), ns * sizeof(long long), hipMemcpyHostToDevice));
+    CUMF_HIP_CHECK(hipMemcpy(l->d_free + ns * sizeof(long long), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+    l->d_seg_begin = reinterpret_cast<long long*>(l->d_free);
+    int* d = reinterpret_cast<int*>(l->d_free + ns * sizeof(long long));
+    l->d_seg_row = d;
+    l->d_seg_len = d + ns;
+    l->d_row_seg0 = d + 2 * ns;
+    l->d_row_nseg = l->d_row_seg0 + rows;
+    l->d_row_len = l->d_row_nseg + rows;
+  }
+  l->n_seg = (long)ns;
+  l->free_built = true;
+  return 0;
+}
+
 ImplicitArgs base_implicit_args(const cumf_plan* p, const int* colidx, const float* val, const float* gather, const float* G,
                                 int f, float lambda, float alpha, int reg_mode) {
   ImplicitArgs a{};
@@ -118,11 +182,11 @@ ImplicitArgs base_implicit_args(const cumf_plan* p, const int* colidx, const flo
   return a;
 }
 
-int check_args(const char* who, const cumf_plan* p, int f, int reg_mode) {
-  if (!p || f != p->f || !implicit_f_ok(f) ||
+int check_args(const char* who, const cumf_plan* p, int f, int reg_mode, int max_f = 128) {
+  if (!p || f != p->f || !(max_f > 128 ? matfree_f_ok(f) : implicit_f_ok(f)) ||
       (reg_mode != CUMF_IMPLICIT_REG_WEIGHTED && reg_mode != CUMF_IMPLICIT_REG_PLAIN)) {
-    fprintf(stderr, "%s: needs a plan of the same f, even 8 <= f <= 128 (got %d) and reg_mode 0 or 1 (got %d)\n", who, f,
-            reg_mode);
+    fprintf(stderr, "%s: needs a plan of the same f, even 8 <= f <= %d (got %d) and reg_mode 0 or 1 (got %d)\n", who, max_f,
+            f, reg_mode);
     return (int)hipErrorInvalidValue;
   }
   return 0;
@@ -142,13 +206,58 @@ int scratch(hipStream_t stream, int kind, size_t count, T** out) {
 //   CG  the plan's short whole rows (its last n_short items, at most kShortRow entries) run the Gram-free CG; the other rows
 //       are materialised into a compact batch, their warm starts gathered, solved by the batched CG and scattered back.
 //   Both then set the rows without stored entries to 0.
+//   CG_MATFREE  no system is formed: every row runs the operator-only CG of als_implicit_free.hip (sparse pass over the row's
+//       segments, row pass with G v on the matrix pipe and the CG updates), which also sets the empty rows to 0.
 struct ImplicitRoute {
   bool materialise_all;  // LU
+  bool matfree;          // CG_MATFREE
   long n_short;          // CG: items [n_items - n_short, n_items) on the Gram-free CG
 };
 ImplicitRoute implicit_route(const cumf_plan* p, int solver) {
-  if (solver == CUMF_SOLVER_LU) return ImplicitRoute{true, 0};
-  return ImplicitRoute{false, p->n_short};
+  if (solver == CUMF_SOLVER_LU) return ImplicitRoute{true, false, 0};
+  if (solver == CUMF_SOLVER_CG_MATFREE) return ImplicitRoute{false, true, 0};
+  return ImplicitRoute{false, false, p->n_short};
+}
+
+// The matrix-free half-iteration: done flags zeroed, then cg_iters + 1 passes (ImplicitFreeArgs); scratch from the pool.
+int update_matfree(cumf_plan* p, ImplicitLists* l, const int* colidx, const float* val, const float* gather, const float* G,
+                   float* update, int f, float lambda, float alpha, int reg_mode, int cg_iters, hipStream_t s) {
+  int rc = free_lists(p, l);
+  if (rc) return rc;
+  const long rows = p->row_end - p->row_begin;
+  if (rows <= 0) return 0;
+  ImplicitFreeArgs a{};
+  a.seg_row = l->d_seg_row;
+  a.seg_begin = l->d_seg_begin;
+  a.seg_len = l->d_seg_len;
+  a.row_seg0 = l->d_row_seg0;
+  a.row_nseg = l->d_row_nseg;
+  a.row_len = l->d_row_len;
+  a.rows = rows;
+  a.nseg = l->n_seg;
+  a.colidx = colidx;
+  a.val = val;
+  a.gather = gather;
+  a.G = G;
+  a.x = update + (size_t)p->row_begin * f;
+  a.f = f;
+  a.lambda = lambda;
+  a.alpha = alpha;
+  a.reg_mode = reg_mode;
+  float *vec = nullptr, *part = nullptr, *words = nullptr;
+  if ((rc = scratch(s, kScratchImpTT, 2 * (size_t)rows * f, &vec)) ||
+      (rc = scratch(s, kScratchImpSlots, 2 * (size_t)a.nseg * f, &part)) || (rc = scratch(s, kScratchImpX, 2 * (size_t)rows, &words)))
+    return rc;
+  a.r = vec;
+  a.p = vec + (size_t)rows * f;
+  a.part = part;
+  a.bpart = part + (size_t)a.nseg * f;
+  a.rs = words;
+  a.done = reinterpret_cast<int*>(words + rows);
+  CUMF_HIP_CHECK(hipMemsetAsync(a.done, 0, (size_t)rows * sizeof(int), s));
+  const int steps = cg_iters > 0 ? cg_iters : 0;
+  for (int k = 0; k <= steps; ++k) CUMF_HIP_CHECK(launch_implicit_free_pass(a, k, steps, s));
+  return 0;
 }
 
 }  // namespace
@@ -162,13 +271,11 @@ int cumf::plan_empty_rows(cumf_plan* p, const int** rows, long* count) {
   return 0;
 }
 
-extern "C" int cumf_implicit_available(int f, int solver) {
-  return implicit_f_ok(f) && (solver == CUMF_SOLVER_CG || solver == CUMF_SOLVER_LU);
-}
+extern "C" int cumf_implicit_available(int f, int solver) { return solver_f_ok(f, solver); }
 
 extern "C" int cumf_implicit_gram(const float* table, long rows, int f, float* G, void* stream) {
-  if (!implicit_f_ok(f) || rows < 0 || !G || (rows > 0 && !table)) {
-    fprintf(stderr, "cumf_implicit_gram: needs even 8 <= f <= 128 (got %d) and rows >= 0\n", f);
+  if (!matfree_f_ok(f) || rows < 0 || !G || (rows > 0 && !table)) {
+    fprintf(stderr, "cumf_implicit_gram: needs even 8 <= f <= 512 (got %d) and rows >= 0\n", f);
     return (int)hipErrorInvalidValue;
   }
   const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -198,7 +305,7 @@ extern "C" int cumf_get_hermitian_implicit(const cumf_plan_t* p, const int* coli
 extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx, const float* val, const float* gather,
                                         const float* G, float* update, int f, float lambda, float alpha, int reg_mode,
                                         int solver, int cg_iters, void* stream) {
-  int rc = check_args("cumf_als_update_implicit", pc, f, reg_mode);
+  int rc = check_args("cumf_als_update_implicit", pc, f, reg_mode, solver == CUMF_SOLVER_CG_MATFREE ? 512 : 128);
   if (rc) return rc;
   if (!cumf_implicit_available(f, solver)) {
     fprintf(stderr, "cumf_als_update_implicit: unknown solver %d\n", solver);
@@ -210,6 +317,7 @@ extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const ImplicitRoute r = implicit_route(p, solver);
   ScratchLease lease;
+  if (r.matfree) return update_matfree(p, l, colidx, val, gather, G, update, f, lambda, alpha, reg_mode, cg_iters, s);
   ImplicitArgs a = base_implicit_args(p, colidx, val, gather, G, f, lambda, alpha, reg_mode);
   a.update = update;
   a.cg_iters = cg_iters;
@@ -249,9 +357,9 @@ extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx
 
 extern "C" int cumf_implicit_loss(const int* rowptr, const int* colidx, const float* val, const float* XT, const float* thetaT,
                                   long m, long n, int f, float lambda, float alpha, int reg_mode, double* out, void* stream) {
-  if (!implicit_f_ok(f) || m < 0 || n < 0 || !out ||
+  if (!matfree_f_ok(f) || m < 0 || n < 0 || !out ||
       (reg_mode != CUMF_IMPLICIT_REG_WEIGHTED && reg_mode != CUMF_IMPLICIT_REG_PLAIN)) {
-    fprintf(stderr, "cumf_implicit_loss: needs even 8 <= f <= 128 (got %d), m, n >= 0 and reg_mode 0 or 1\n", f);
+    fprintf(stderr, "cumf_implicit_loss: needs even 8 <= f <= 512 (got %d), m, n >= 0 and reg_mode 0 or 1\n", f);
     return (int)hipErrorInvalidValue;
   }
   const hipStream_t s = static_cast<hipStream_t>(stream);

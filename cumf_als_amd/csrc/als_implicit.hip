@@ -443,12 +443,17 @@ static unsigned grid_for(long long work, long long per_block, long long cap) {
 
 size_t implicit_gram_part_floats(long rows, int f) {
   const size_t FP = 16 * (size_t)((f + 15) / 16);
-  return (size_t)((rows + kImpGramSlab - 1) / kImpGramSlab) * FP * FP;
+  const long slab = implicit_gram_slab(f);
+  return (size_t)((rows + slab - 1) / slab) * FP * FP;
 }
 
 hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, float* G, double* G64, hipStream_t stream) {
-  const int FT = (f + 15) / 16, nslab = (int)((rows + kImpGramSlab - 1) / kImpGramSlab);
-  if (nslab > 0) {
+  const long slab = implicit_gram_slab(f);
+  const int FT = (f + 15) / 16, nslab = (int)((rows + slab - 1) / slab);
+  if (nslab > 0 && FT > 8) {  // 128 < f <= 512: the tiles spread over a second grid dimension (als_implicit_free.hip)
+    const hipError_t e = launch_implicit_gram_wide(Y, rows, f, part, stream);
+    if (e != hipSuccess) return e;
+  } else if (nslab > 0) {
     const hipError_t e = with_nb<1, 8>(FT, [&](auto ft) {
       return launch_kernel(implicit_gram_partial_kernel<decltype(ft)::value>, dim3((unsigned)nslab), dim3(kImpThreads), 0,
                            stream, Y, (long long)rows, f, part);

@@ -351,6 +351,43 @@ hipError_t launch_implicit_zero_rows(const int* rows, long count, int f, float* 
 hipError_t launch_implicit_loss(const int* rowptr, const int* colidx, const float* val, const float* XT, const float* thetaT,
                                 long m, int f, float lambda, float alpha, int reg_mode, const double* Gx, const double* Gy,
                                 double* part, double* out, hipStream_t stream);
+// Table rows per workgroup (and fp32 partial) of the Gram: kImpGramSlab up to f = 128, more above, where a partial is f x f.
+inline long implicit_gram_slab(int f) {
+  const int FT = (f + 15) / 16;
+  return FT <= 8 ? kImpGramSlab : (long)kImpGramSlab * ((FT + 7) / 8);
+}
+// The Gram partials of a table with 128 < f <= 512 (als_implicit_free.hip; launch_implicit_gram reduces them)
+hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* part, hipStream_t stream);
+// The matrix-free CG (als_implicit_free.hip): rows are the plan's, indexed by row - row_begin; a row's stored entries are cut
+// into segments of at most kFreeSeg entries at fixed offsets from its start.
+constexpr int kFreeSeg = 2048;
+constexpr int kFreeRows = 32;  // rows per workgroup of the row pass
+struct ImplicitFreeArgs {
+  const int* seg_row;            // nseg: row of each segment
+  const long long* seg_begin;    // ... its first entry (index into colidx / val)
+  const int* seg_len;
+  const int* row_seg0;           // rows: first segment of each row (its segments are consecutive)
+  const int* row_nseg;
+  const int* row_len;            // stored entries of the row (0: x = 0)
+  long long rows, nseg;
+  const int* colidx;
+  const float* val;
+  const float* gather;
+  const float* G;
+  float* x;      // update + row_begin * f: warm start in, solution out
+  float* r;      // rows x f residuals
+  float* p;      // rows x f search directions
+  float* part;   // nseg x f: T^T (w o T v) of each segment
+  float* bpart;  // nseg x f: the segment's part of b (first pass)
+  float* rs;     // rows: r.r
+  int* done;     // rows: 1 once the row's CG has ended (zeroed before the first pass)
+  int f;
+  float lambda, alpha;
+  int reg_mode;
+};
+// step 0: the sparse pass with v = x (and b), then r = b - A x, p = r; step k >= 1: CG step k with A p.  step == cg_iters: the
+// last pass.
+hipError_t launch_implicit_free_pass(const ImplicitFreeArgs& a, int step, int cg_iters, hipStream_t stream);
 // Work lists of the implicit-feedback half-iterations, built on a plan at first use (als_implicit.cpp).
 struct ImplicitLists;
 void free_implicit_lists(ImplicitLists* lists);

@@ -548,7 +548,7 @@ extern "C" int cumf_last_kernel_name(char* buf, int cap) {
 // Can one fused call (RHS + Gram + solve) handle (f, solver)?  Even f with a route (route_for, als_route.cpp).
 extern "C" int cumf_fused_available(int f, int solver) {
   const int mode = solver == CUMF_SOLVER_LU ? kModeLU : kModeCG;
-  if (f <= 0 || (f % 2) != 0) return 0;
+  if (f <= 0 || (f % 2) != 0 || (solver != CUMF_SOLVER_CG && solver != CUMF_SOLVER_LU)) return 0;
   return route_for(f, mode, PlanFacts{}, switches()).path != kPathNone;
 }
 
@@ -590,7 +590,7 @@ extern "C" int cumf_als_update_fused(const cumf_plan_t* p, const int* colidx, co
 // Can the half-iteration of this plan also deliver the train SSE of its rows (cumf_als_update_fused_sse)?  Where every
 // solver on its route adds it (Route::sse; route_for spells out the two gaps).
 extern "C" int cumf_fused_sse_available(const cumf_plan_t* p, int solver) {
-  if (!p) return 0;
+  if (!p || (solver != CUMF_SOLVER_CG && solver != CUMF_SOLVER_LU)) return 0;
   return route_for(p->f, solver == CUMF_SOLVER_LU ? kModeLU : kModeCG, plan_facts(p), switches()).sse;
 }
 
@@ -721,6 +721,10 @@ extern "C" int cumf_quadratic_sse_terms(const float* A, const float* b, const fl
 extern "C" int cumf_check_gather_table(long gather_rows, int f, int solver, int materialize) {
   const int mode = materialize ? kModeMaterialize : (solver == CUMF_SOLVER_LU ? kModeLU : kModeCG);
   if (gather_rows < 0 || f <= 0) return (int)hipErrorInvalidValue;
+  if (solver != CUMF_SOLVER_CG && solver != CUMF_SOLVER_LU) {
+    fprintf(stderr, "cumf_als: solver %d is not an explicit-feedback solver (CUMF_SOLVER_CG or CUMF_SOLVER_LU)\n", solver);
+    return (int)hipErrorInvalidValue;
+  }
   if (f > kMaxF) return 0;  // als_generic.hip: 64-bit gather addresses
   const Path path = route_for(f, mode, PlanFacts{}, switches()).path;
   if (path == kPathOneWave || path == kPathTwoWave) return 0;  // the wave kernels: 64-bit addresses too

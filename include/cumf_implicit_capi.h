@@ -11,8 +11,9 @@
  *
  * Conventions of cumf_als_capi.h: DEVICE pointers of the calling process, `stream` a hipStream_t passed as void* (NULL =
  * the default stream), 0 on success or a HIP error code after printing file/line to stderr, no CPU fallback.  Plans are
- * the cumf_plan_t of cumf_als_capi.h.  Scope: even f with 8 <= f <= 128 on one GPU; anything else is refused.  Every
- * result is bit-identical from run to run (fixed-order reductions, no float atomics).
+ * the cumf_plan_t of cumf_als_capi.h.  Scope: one GPU; even f with 8 <= f <= 512 for CUMF_SOLVER_CG_MATFREE,
+ * cumf_implicit_gram and cumf_implicit_loss, even f with 8 <= f <= 128 for everything else; anything else is refused.
+ * Every result is bit-identical from run to run (fixed-order reductions, no float atomics).
  */
 #ifndef CUMF_IMPLICIT_CAPI_H_
 #define CUMF_IMPLICIT_CAPI_H_
@@ -25,11 +26,16 @@ extern "C" {
 
 enum { CUMF_IMPLICIT_REG_WEIGHTED = 0, CUMF_IMPLICIT_REG_PLAIN = 1 };
 
-/* 1 when the implicit entry points take (f, solver): even f in [8, 128], solver CUMF_SOLVER_CG or CUMF_SOLVER_LU. */
+/* The third implicit solver (after CUMF_SOLVER_CG = 0 and CUMF_SOLVER_LU = 1 of cumf_als_capi.h); implicit entry points only. */
+enum { CUMF_SOLVER_CG_MATFREE = 2 };
+
+/* 1 when the implicit entry points take (f, solver): even f in [8, 128] with CUMF_SOLVER_CG or CUMF_SOLVER_LU, even f in
+ * [8, 512] with CUMF_SOLVER_CG_MATFREE. */
 int cumf_implicit_available(int f, int solver);
 
-/* G = table^T table of a rows x f fp32 table: f x f fp32, both triangles, exactly symmetric.  fp32 matrix-pipe products
- * per slab of rows, the slab partials summed in slab order in fp64. */
+/* G = table^T table of a rows x f fp32 table (even 8 <= f <= 512): f x f fp32, both triangles, exactly symmetric.  fp32
+ * matrix-pipe products per slab of rows (1 024 rows up to f = 128, more above), the slab partials summed in slab order
+ * in fp64. */
 int cumf_implicit_gram(const float* table, long rows, int f, float* G, void* stream);
 
 /* The materialised systems of the plan's rows: tt receives (row_end - row_begin) x f x f fp32 (row-major, both
@@ -44,7 +50,9 @@ int cumf_get_hermitian_implicit(const cumf_plan_t* plan, const int* colidx, cons
  *                   T the row's gathered block); longer rows are materialised and solved by cumf_cg_solve_batched.  The
  *                   recurrence of cumf_cg_solve_batched: warm start, at most cg_iters steps, exit when r.r < 1e-4.
  *   CUMF_SOLVER_LU: every row materialised and solved by cumf_lu_solve_batched.
- * Rows without stored entries are set to 0 by both. */
+ *   CUMF_SOLVER_CG_MATFREE (even 8 <= f <= 512): no row forms A_u; every step evaluates A p = G p + T^T (w o T p) + reg p
+ *                   over the stored entries and G.  The same recurrence, checked per row.
+ * Rows without stored entries are set to 0 by all three. */
 int cumf_als_update_implicit(const cumf_plan_t* plan, const int* colidx, const float* val, const float* gather,
                              const float* G, float* update, int f, float lambda, float alpha, int reg_mode, int solver,
                              int cg_iters, void* stream);

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Times implicit-feedback ALS iterations (ImplicitALSEngine) at the Netflix shape: synthetic ratings from
-datagen.synth_ratings (17 770 x 480 189, 99 M), alpha = 40, weighted lambda, CG with cg_iters = 3 and LU, f = 64 and 100.
-Device-event timing of each half-iteration after warm-up; one JSON line per (f, solver).  Kernel shares come from a
-separate run under `rocprofv3 --kernel-trace --stats -- python tools/implicit_time.py --f 100 --solver lu --iters 2`.
-  python tools/implicit_time.py [--f 64 100] [--solver cg lu] [--iters 3] [--warmup 1] [--loss]"""
+datagen.synth_ratings (17 770 x 480 189, 99 M), alpha = 40, weighted lambda, CG with cg_iters = 3 and LU, f = 64 and 100;
+--solver cg_matfree (the operator-only CG) and any even --f up to 512 ("cg" above f = 128 is the same route).
+Device-event timing of each half-iteration after warm-up; one JSON line per (f, solver), with the two floors of a
+matrix-free half-iteration: the gather, (cg_iters + 1) nnz f 4 B at 6.29 TB/s, and the GEMM work, (cg_iters + 1) x
+(2 rows f^2 + 4 nnz f) FLOP at 157.3 TFLOP/s, per side.  Kernel shares come from a separate run under
+`rocprofv3 --kernel-trace --stats -- python tools/implicit_time.py --f 100 --solver lu --iters 2`.
+  python tools/implicit_time.py [--f 64 100] [--solver cg lu cg_matfree] [--iters 3] [--warmup 1] [--loss]"""
 import argparse
 import json
 import os
@@ -29,6 +32,9 @@ def main() -> int:
     r = datagen.synth_ratings(shp["m"], shp["n"], shp["nnz"], shp["nnz_test"], seed=0, device="cuda")
     for f in a.f:
         for solver in a.solver:
+            if not als.implicit_available(f, "cg_matfree" if solver == "cg" and f > 128 else solver):
+                print(json.dumps({"f": f, "solver": solver, "skipped": "not available"}), flush=True)
+                continue
             eng = als.ImplicitALSEngine(r, f, shp["lam"], a.alpha, solver=solver, cg_iters=3)
             eng.init_factors()
             eng.iterate(a.warmup)
@@ -50,6 +56,10 @@ def main() -> int:
             out = {"shape": a.shape, "f": f, "solver": solver, "alpha": a.alpha, "cg_iters": 3,
                    "ms_per_iter_median": round(it[len(it) // 2], 3), "ms_per_iter_min": round(it[0], 3),
                    "x_ms": [round(v, 3) for v in xs], "theta_ms": [round(v, 3) for v in ts]}
+            k = 3 + 1
+            out["gather_floor_ms_per_side"] = round(k * shp["nnz"] * f * 4 / 6.29e12 * 1e3, 3)
+            out["gemm_floor_ms"] = {side: round(k * (2 * rows * f * f + 4 * shp["nnz"] * f) / 157.3e12 * 1e3, 3)
+                                    for side, rows in (("x", shp["m"]), ("theta", shp["n"]))}
             if a.loss:
                 out["loss"] = losses
             print(json.dumps(out), flush=True)
