@@ -15,6 +15,9 @@
 * `topk`, `ranking_metrics` (include/cumf_topk_capi.h): the k best candidates per query, scored by a fused HIP kernel
   that never writes the score matrix, and precision / recall / NDCG@k against held-out entries; both engines expose them
   as `recommend(k, side)` and `ranking_metrics(k, side)`.
+* `heldout_ranks`, `rank_metrics` (include/cumf_rank_capi.h): the rank of every held-out entry among all eligible
+  candidates, by the same fused scoring, and AUC / MPR / MRR / MAP / precision, recall and NDCG at any cut-off from those
+  ranks; both engines expose them as `heldout_ranks(side)` and `full_ranking_metrics(side, ks)`.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -598,6 +601,69 @@ def heldout_csr(row, col, val, rows: int):
     return rowptr, col[order].to(torch.int32).contiguous(), val[order].to(torch.float32).contiguous()
 
 
+# ---------------------------------------------------------------------------------------
+# full-ranking evaluation (include/cumf_rank_capi.h)
+# ---------------------------------------------------------------------------------------
+
+def rank_available(f: int) -> bool:
+    return bool(_libmod.load().cumf_rank_available(int(f)))
+
+
+def heldout_ranks(query, cand, test_rowptr, test_colidx, exclude=None, out=None):
+    """The rank of every held-out entry among all eligible candidates of its query (cumf_heldout_ranks): `query` rows x f
+    and `cand` ncand x f fp32 on the device, scores and order as `topk`; (test_rowptr, test_colidx) the held-out CSR
+    (ascending and unique within each row), `exclude` an optional (rowptr, colidx) CSR of candidates that do not count.
+    Returns (ranks int32 parallel to test_colidx, n_eligible int32 per query): rank 0 is the best position, -1 marks an
+    entry outside the table, excluded, or with a NaN score.  Entries outside [test_rowptr[0], test_rowptr[rows]) keep
+    what `out[0]` holds (-1 without `out`)."""
+    import torch
+
+    rows, f = int(query.shape[0]), int(query.shape[1])
+    if int(cand.shape[1]) != f:
+        raise ValueError(f"query and candidate tables differ in f ({f} vs {int(cand.shape[1])})")
+    if int(test_rowptr.shape[0]) != rows + 1:
+        raise ValueError(f"test_rowptr needs rows + 1 = {rows + 1} entries, got {int(test_rowptr.shape[0])}")
+    n_test = int(test_colidx.shape[0])
+    if out is None:
+        out = (torch.full((n_test,), -1, dtype=torch.int32, device=query.device),
+               torch.empty((rows,), dtype=torch.int32, device=query.device))
+    ranks, n_eligible = out
+    if int(ranks.shape[0]) != n_test or int(n_eligible.shape[0]) != rows:
+        raise ValueError("out must be (ranks parallel to test_colidx, n_eligible per query)")
+    rp, rp64, ci = None, 0, None
+    if exclude is not None:
+        rp, rp64 = _rowptr(exclude[0])
+        ci = _dp(exclude[1], torch.int32)
+    tp, tp64 = _rowptr(test_rowptr)
+    _libmod.check(_libmod.load().cumf_heldout_ranks(
+        _dp(query, torch.float32), rows, _dp(cand, torch.float32), int(cand.shape[0]), f, rp, rp64, ci, tp, tp64,
+        _dp(test_colidx, torch.int32), n_test, _dp(ranks, torch.int32), _dp(n_eligible, torch.int32), _stream()),
+        "cumf_heldout_ranks")
+    return ranks, n_eligible
+
+
+def rank_metrics(ranks, n_eligible, test_rowptr, test_val=None, ks=(10, 100, 1000)) -> dict:
+    """AUC, MPR (expected percentile rank), MRR, MAP and precision / recall / NDCG at every cut-off of `ks`
+    (cumf_rank_metrics) from what `heldout_ranks` returns; an entry is relevant when its value is > 0, or always without
+    values.  "precision", "recall" and "ndcg" are dicts keyed by the cut-off."""
+    import torch
+
+    ks = [int(k) for k in ks]
+    rows = int(n_eligible.shape[0])
+    out = torch.zeros(6 + 3 * len(ks), dtype=torch.float64, device=ranks.device)
+    rp, rp64 = _rowptr(test_rowptr)
+    _libmod.check(_libmod.load().cumf_rank_metrics(
+        _dp(ranks, torch.int32), _dp(n_eligible, torch.int32), rows, rp, rp64,
+        None if test_val is None else _dp(test_val, torch.float32), int(ranks.shape[0]), (C.c_int * len(ks))(*ks), len(ks),
+        _dp(out, torch.float64), _stream()), "cumf_rank_metrics")
+    v = out.tolist()
+    res = {"queries": int(v[0]), "auc_queries": int(v[1]), "auc": v[2], "mpr": v[3], "mrr": v[4], "map": v[5],
+           "precision": {}, "recall": {}, "ndcg": {}}
+    for c, k in enumerate(ks):
+        res["precision"][k], res["recall"][k], res["ndcg"][k] = v[6 + 3 * c:9 + 3 * c]
+    return res
+
+
 class _Recommender:
     """recommend / ranking_metrics of a trained engine (`XT`, `thetaT`, ratings `r`), shared by both engines.  Side "x":
     the rows of XT are the queries and the rows of thetaT the candidates, the training CSR excluded; side "theta" the
@@ -621,6 +687,22 @@ class _Recommender:
         ids, _ = self.recommend(k, side, exclude_seen)
         row, col, rows = self._side(side)[3]
         return ranking_metrics(ids, *heldout_csr(row, col, self.r.test_data, rows))
+
+    def _heldout(self, side, exclude_seen):
+        query, cand, seen, (row, col, rows) = self._side(side)
+        rowptr, colidx, val = heldout_csr(row, col, self.r.test_data, rows)
+        ranks, n_eligible = heldout_ranks(query, cand, rowptr, colidx, seen if exclude_seen else None)
+        return ranks, n_eligible, rowptr, colidx, val
+
+    def heldout_ranks(self, side: str = "x", exclude_seen: bool = True):
+        """(ranks, n_eligible, rowptr, colidx) of the engine's test set among all candidates of `side`, its training
+        entries left out: ranks is parallel to colidx, the test set as the CSR `heldout_csr` makes of it."""
+        return self._heldout(side, exclude_seen)[:4]
+
+    def full_ranking_metrics(self, side: str = "x", ks=(10, 100, 1000), exclude_seen: bool = True) -> dict:
+        """rank_metrics of heldout_ranks(side) against the engine's test set."""
+        ranks, n_eligible, rowptr, _, val = self._heldout(side, exclude_seen)
+        return rank_metrics(ranks, n_eligible, rowptr, val, ks)
 
 
 class ALSEngine(_Recommender):

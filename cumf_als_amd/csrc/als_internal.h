@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <type_traits>
 
@@ -295,6 +296,11 @@ enum {
   // non-negative ALS (als_nnls.cpp): materialised systems, right-hand sides
   kScratchNnlsTT = 12,
   kScratchNnlsRhs = 13,
+  // full ranking (als_rank.cpp): sorted held-out keys, buckets, valid thresholds per query, per-query metrics
+  kScratchRankKeys = 14,
+  kScratchRankHist = 15,
+  kScratchRankValid = 16,
+  kScratchRankMetrics = 17,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 struct ScratchLease {
@@ -427,6 +433,72 @@ hipError_t launch_topk_merge(const unsigned long long* part, long long rows, int
 // part: 4 x rows doubles; out: (count, precision, recall, ndcg)
 hipError_t launch_topk_metrics(const int* ids, long long rows, int k, const void* rowptr, int rowptr64, const int* colidx,
                                const float* val, double* part, double* out, hipStream_t stream);
+
+// How a scoring kernel cuts the work, decided here only: query blocks of kTopkQB x slabs of the candidates, on a persistent
+// grid of at most one workgroup per resident slot.  A query block alone takes all candidates (one slab) when there are at
+// least two blocks per slot; fewer blocks (few queries, e.g. the items x users side of Netflix) split the candidates into
+// slabs until there are, but no slab below kTopkMinSlab candidates.  The result does not depend on the cut.
+constexpr long long kTopkMinSlab = 16 * kTopkNC;  // candidates per slab at least: the per-slab set-up stays a small part
+struct TopkCut {
+  int nslab;
+  long long slab_len;
+  long long n_items;
+  long long grid;
+};
+inline TopkCut topk_cut(long long rows, long long ncand, int cus, int wgs_per_cu) {
+  const long long qblocks = (rows + kTopkQB - 1) / kTopkQB;
+  const long long slots = (long long)cus * wgs_per_cu;
+  long long nslab = 1;
+  if (qblocks < 2 * slots) nslab = (2 * slots + qblocks - 1) / qblocks;
+  nslab = std::min(nslab, std::max(1LL, (ncand + kTopkMinSlab - 1) / kTopkMinSlab));
+  long long slab_len = (ncand + nslab - 1) / nslab;
+  slab_len = std::max((long long)kTopkNC, (slab_len + kTopkNC - 1) / kTopkNC * kTopkNC);
+  nslab = std::max(1LL, (ncand + slab_len - 1) / slab_len);
+  const long long items = qblocks * nslab;
+  return TopkCut{(int)nslab, slab_len, items, std::min(items, slots)};
+}
+
+// ---- Full ranking: held-out ranks and their metrics (als_rank.hip kernels, als_rank.cpp host side; include/cumf_rank_capi.h)
+constexpr int kRankPoolW = 768;            // held-out keys (and buckets) a wave keeps in LDS for its kTopkQW queries
+constexpr int kRankPool = 4 * kRankPoolW;  // ... per workgroup; a wave whose queries have more works on the global arrays
+constexpr int kRankMaxK = 16;              // cut-offs per cumf_rank_metrics call
+constexpr int kRankCols = 7;               // per-query metric columns in front of the 3 per cut-off
+struct RankArgs {
+  const float* Q;
+  long long rows;
+  const float* C;
+  long long ncand;
+  int f;
+  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
+  int rowptr64;
+  const int* excl_colidx;
+  int vec;                  // C rows may be read as float4 (f % 4 == 0, 16-byte aligned)
+  const void* test_rowptr;  // rows + 1 entries, int32 or int64 (test_rowptr64)
+  int test_rowptr64;
+  const int* test_colidx;
+  long long n_test;         // entries of test_colidx (and of keys, hist, ranks)
+  int nslab;
+  long long slab_len;       // candidates per slab, a multiple of kTopkNC
+  long long n_items;        // query blocks x slabs
+  unsigned long long* keys; // per held-out entry: its key (0: not eligible), sorted in descending order within each row
+  int* hist;                // per row: bucket b = eligible candidates below exactly b of the row's valid keys
+  int* nvalid;              // per query: its non-zero keys
+  int* ranks;
+  int* n_eligible;
+};
+struct RankKs {
+  int n;
+  int k[kRankMaxK];
+};
+int rank_count_occupancy(bool multi);  // workgroups per CU of the count kernel
+// keys + ranks = -1 of the entries that are not eligible, the sort of each row, nvalid; hist and n_eligible zeroed
+hipError_t launch_rank_thresholds(const RankArgs& a, hipStream_t stream);
+hipError_t launch_rank_count(const RankArgs& a, long long grid, hipStream_t stream);
+hipError_t launch_rank_finish(const RankArgs& a, hipStream_t stream);
+// keys: n_test; part: (kRankCols + 3 ks.n) x rows doubles; out: 6 + 3 ks.n doubles
+hipError_t launch_rank_metrics(const int* ranks, const int* n_eligible, long long rows, const void* rowptr, int rowptr64,
+                               const float* val, long long n_test, const RankKs& ks, unsigned long long* keys, double* part,
+                               double* out, hipStream_t stream);
 
 // ---- Non-negative least squares (als_nnls.hip kernel, als_nnls.cpp host side; include/cumf_nnls_capi.h)
 constexpr int kNnlsMaxF = 128;

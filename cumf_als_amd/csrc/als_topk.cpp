@@ -1,5 +1,5 @@
 // als_topk.cpp -- host side of top-k recommendation and ranking metrics (include/cumf_topk_capi.h): argument checks, the slab
-// cut, scratch, launches.  Kernels: als_topk.hip.
+// cut (topk_cut, als_internal.h), scratch, launches.  Kernels: als_topk.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,31 +11,6 @@
 using namespace cumf;
 
 namespace {
-
-constexpr long long kTopkMinSlab = 16 * kTopkNC;  // candidates per slab at least: the list fill stays a small part of a slab
-
-// How the score kernel cuts the work, decided here only: query blocks of kTopkQB x slabs of the candidates, on a persistent
-// grid of at most one workgroup per resident slot.  A query block alone takes all candidates (one slab) when there are at
-// least two blocks per slot; fewer blocks (few queries, e.g. the items x users side of Netflix) split the candidates into
-// slabs until there are, but no slab below kTopkMinSlab candidates.  The result does not depend on the cut.
-struct TopkCut {
-  int nslab;
-  long long slab_len;
-  long long n_items;
-  long long grid;
-};
-TopkCut topk_cut(long long rows, long long ncand, int cus, int wgs_per_cu) {
-  const long long qblocks = (rows + kTopkQB - 1) / kTopkQB;
-  const long long slots = (long long)cus * wgs_per_cu;
-  long long nslab = 1;
-  if (qblocks < 2 * slots) nslab = (2 * slots + qblocks - 1) / qblocks;
-  nslab = std::min(nslab, std::max(1LL, (ncand + kTopkMinSlab - 1) / kTopkMinSlab));
-  long long slab_len = (ncand + nslab - 1) / nslab;
-  slab_len = std::max((long long)kTopkNC, (slab_len + kTopkNC - 1) / kTopkNC * kTopkNC);
-  nslab = std::max(1LL, (ncand + slab_len - 1) / slab_len);
-  const long long items = qblocks * nslab;
-  return TopkCut{(int)nslab, slab_len, items, std::min(items, slots)};
-}
 
 bool topk_ok(int f, int k) { return f >= 1 && f <= kTopkMaxF && k >= 1 && k <= kTopkMaxK; }
 

@@ -17,26 +17,12 @@
 
 #include "als_device.h"
 #include "als_internal.h"
+#include "als_score.h"
 
 namespace cumf {
 
 // (no anonymous namespace: cumf_last_kernel_name reports the kernels as cumf::topk_*)
-typedef unsigned long long topk_key;
-
-// score -> 32 bits whose unsigned order is the float order (-0 is taken as +0, so equal scores tie on the index)
-__device__ __forceinline__ unsigned topk_ord(float s) {
-  unsigned u = __float_as_uint(s + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ topk_key topk_make_key(float s, int id) {
-  return ((topk_key)topk_ord(s) << 32) | (topk_key)(~(unsigned)id);
-}
-__device__ __forceinline__ float topk_key_score(topk_key k) {
-  const unsigned o = (unsigned)(k >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ int topk_key_id(topk_key k) { return (int)~(unsigned)k; }
-// key 0 is below every real key (ord(-inf) = 0x007fffff): an empty slot
+// the key of the total order, topk_wave_sync, topk_rowptr, topk_stage and topk_load_query: als_score.h
 
 __device__ __forceinline__ topk_key topk_shfl_xor(topk_key v, int d) {
   const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, d, 64);
@@ -85,16 +71,6 @@ __device__ __forceinline__ topk_key topk_element(const topk_key (&v)[4], int e) 
   return ((topk_key)hi << 32) | lo;
 }
 
-// Orders this wave's global stores and LDS operations before its following loads (lanes exchange data through both).
-__device__ __forceinline__ void topk_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ long long topk_rowptr(const void* rp, int is64, long long i) {
-  return is64 ? static_cast<const long long*>(rp)[i] : (long long)static_cast<const int*>(rp)[i];
-}
-
 constexpr float kTopkOpen = __builtin_nanf("");  // threshold of a list with fewer than k entries: everything passes
 
 // Merge the buffer of query slot qi into its sorted list (whole wave): list[0, nlist) + buf[0, cnt) -> the best min(k, .)
@@ -124,48 +100,6 @@ __device__ __forceinline__ void topk_merge_query(topk_key* __restrict__ list, to
     thr[qi] = nn == k ? topk_key_score(kth) : kTopkOpen;
   }
   topk_wave_sync();
-}
-
-// Stage candidates [c0, c0 + nc) x features [j0, j0 + fc) into cs (kTopkNC rows of kTopkPitch floats).  Within each group of
-// 16 features, feature 16 b + 4 t + kq sits at 16 b + 4 kq + t: the lanes of k-group kq read steps 4 b .. 4 b + 3 with one
-// 16-byte load.  Zeros beyond nc and up to the next multiple of 16 features.
-__device__ __forceinline__ void topk_stage(float* cs, const float* __restrict__ C, int f, long long c0, int nc, int j0, int fc,
-                                           bool vec) {
-  const int fcp = (fc + 15) & ~15;
-  const int groups = fcp >> 2;  // float4 groups per row
-  for (int e = threadIdx.x; e < kTopkNC * groups; e += kTopkThreads) {
-    const int r = e / groups, g = e - r * groups;
-    const int jj = 4 * g;
-    float x[4] = {0.f, 0.f, 0.f, 0.f};
-    if (r < nc) {
-      const float* src = C + (size_t)(c0 + r) * f + j0 + jj;
-      if (vec && jj < fc) {
-        const float4 w = *reinterpret_cast<const float4*>(src);
-        x[0] = w.x, x[1] = w.y, x[2] = w.z, x[3] = w.w;
-      } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) x[t] = jj + t < fc ? src[t] : 0.f;
-      }
-    }
-    float* dst = cs + r * kTopkPitch + 16 * (g >> 2) + (g & 3);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) dst[4 * t] = x[t];
-  }
-}
-
-// A lane's query fragments of features [j0, j0 + fc): qf[qt][s] = Q[q][j0 + 4 s + (lane >> 4)], q = 16 qt + (lane & 15) of the wave.
-__device__ __forceinline__ void topk_load_query(float (&qf)[2][kTopkJC / 4], const TopkArgs& a, long long wq0, int j0, int fc,
-                                                int lane) {
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const long long q = wq0 + 16 * qt + (lane & 15);
-    const float* row = a.Q + (size_t)(q < a.rows ? q : 0) * a.f + j0;
-#pragma unroll
-    for (int s = 0; s < kTopkJC / 4; ++s) {
-      const int j = 4 * s + (lane >> 4);
-      qf[qt][s] = (q < a.rows && j < fc) ? row[j] : 0.f;
-    }
-  }
 }
 
 template <bool MULTI>  // MULTI: f > kTopkJC, the features in several LDS chunks (query fragments reloaded per chunk)

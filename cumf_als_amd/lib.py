@@ -1,5 +1,5 @@
 """ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h, cumf_dist_capi.h,
-cumf_implicit_capi.h and cumf_topk_capi.h).
+cumf_implicit_capi.h, cumf_topk_capi.h, cumf_nnls_capi.h and cumf_rank_capi.h).
 
 The library is the product: there is no Python or CPU fallback.  `load()` raises
 when the shared object is missing or lacks a declared symbol.
@@ -42,6 +42,8 @@ TOPK_SYMBOLS = ["cumf_topk_available", "cumf_topk", "cumf_ranking_metrics"]
 # every extern "C" symbol declared in include/cumf_nnls_capi.h (non-negative ALS, als_nnls.cpp)
 NNLS_SYMBOLS = ["cumf_nnls_available", "cumf_nnls_solve_batched", "cumf_als_update_nonneg",
                 "cumf_als_update_implicit_nonneg"]
+# every extern "C" symbol declared in include/cumf_rank_capi.h (full-ranking evaluation, als_rank.cpp)
+RANK_SYMBOLS = ["cumf_rank_available", "cumf_heldout_ranks", "cumf_rank_metrics"]
 # C++-linkage drop-in symbols (include/als.h, include/cg.h) under the reference's mangled names
 CXX_SYMBOLS = [
     "_Z5doALSPKiS0_PKfS0_S0_S2_S0_PfS3_S0_S0_S2_iiillfiiii",
@@ -71,7 +73,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  cumf_als_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + TOPK_SYMBOLS + NNLS_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in C_SYMBOLS + DIST_SYMBOLS + IMPLICIT_SYMBOLS + TOPK_SYMBOLS + NNLS_SYMBOLS + RANK_SYMBOLS + CXX_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f"{LIB_PATH} lacks symbols declared in include/: {missing}")
 
@@ -211,6 +213,14 @@ def load():
     lib.cumf_als_update_implicit_nonneg.restype = C.c_int
     lib.cumf_als_update_implicit_nonneg.argtypes = [vp, ip, fp, fp, fp, fp, C.c_int, C.c_float, C.c_float, C.c_int,
                                                     C.c_int, vp, vp]
+    # include/cumf_rank_capi.h
+    lib.cumf_rank_available.restype = C.c_int
+    lib.cumf_rank_available.argtypes = [C.c_int]
+    lib.cumf_heldout_ranks.restype = C.c_int
+    lib.cumf_heldout_ranks.argtypes = [fp, C.c_long, fp, C.c_long, C.c_int, vp, C.c_int, ip, vp, C.c_int, ip, C.c_long, ip,
+                                       ip, vp]
+    lib.cumf_rank_metrics.restype = C.c_int
+    lib.cumf_rank_metrics.argtypes = [ip, ip, C.c_long, vp, C.c_int, fp, C.c_long, C.POINTER(C.c_int), C.c_int, vp, vp]
     host_args = [vp] * 12 + [C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_float, C.c_int, C.c_int, C.c_int,
                              C.c_int]
     lib.cumf_doALS.restype = C.c_float
