@@ -548,6 +548,15 @@ def _rowptr(rowptr):
     return _dp(rowptr), int(rowptr.dtype == torch.int64)
 
 
+def _exclusion(exclude):
+    """(rowptr, is64, colidx) arguments of an optional (rowptr, colidx) exclusion CSR; none: (None, 0, None)."""
+    import torch
+
+    if exclude is None:
+        return None, 0, None
+    return (*_rowptr(exclude[0]), _dp(exclude[1], torch.int32))
+
+
 def topk(query, cand, k: int, exclude=None, out=None):
     """The k best candidates of every query row (cumf_topk): `query` rows x f and `cand` ncand x f fp32 on the device, the
     score of a candidate the fp32 fmaf chain of the dot product in increasing feature order.  `exclude` is an optional
@@ -562,10 +571,7 @@ def topk(query, cand, k: int, exclude=None, out=None):
         out = (torch.empty((rows, k), dtype=torch.int32, device=query.device),
                torch.empty((rows, k), dtype=torch.float32, device=query.device))
     ids, scores = out
-    rp, rp64, ci = None, 0, None
-    if exclude is not None:
-        rp, rp64 = _rowptr(exclude[0])
-        ci = _dp(exclude[1], torch.int32)
+    rp, rp64, ci = _exclusion(exclude)
     _libmod.check(_libmod.load().cumf_topk(
         _dp(query, torch.float32), rows, _dp(cand, torch.float32), int(cand.shape[0]), f, rp, rp64, ci, int(k),
         _dp(ids, torch.int32), _dp(scores, torch.float32), _stream()), "cumf_topk")
@@ -630,10 +636,7 @@ def heldout_ranks(query, cand, test_rowptr, test_colidx, exclude=None, out=None)
     ranks, n_eligible = out
     if int(ranks.shape[0]) != n_test or int(n_eligible.shape[0]) != rows:
         raise ValueError("out must be (ranks parallel to test_colidx, n_eligible per query)")
-    rp, rp64, ci = None, 0, None
-    if exclude is not None:
-        rp, rp64 = _rowptr(exclude[0])
-        ci = _dp(exclude[1], torch.int32)
+    rp, rp64, ci = _exclusion(exclude)
     tp, tp64 = _rowptr(test_rowptr)
     _libmod.check(_libmod.load().cumf_heldout_ranks(
         _dp(query, torch.float32), rows, _dp(cand, torch.float32), int(cand.shape[0]), f, rp, rp64, ci, tp, tp64,
@@ -705,35 +708,21 @@ class _Recommender:
         return rank_metrics(ranks, n_eligible, rowptr, val, ks)
 
 
-class ALSEngine(_Recommender):
-    """A dataset resident in HBM + the two half-iteration plans (single GPU).
+class _Engine(_Recommender):
+    """What the two engines share: a dataset resident in HBM (`r`, a `cumf_als_amd.datagen.Ratings` already on the
+    device), the half-iteration plans of both sides and the factors -- the reference's `thetaT` (n x f) and `XT` (m x f),
+    row-contiguous f-vectors.  An engine adds `_half(plans, colidx, val, gather, update)`, one half-iteration."""
 
-    `r` is a `cumf_als_amd.datagen.Ratings` already on the device.  Factors are the
-    reference's `thetaT` (n x f) and `XT` (m x f), row-contiguous f-vectors.
-    """
-
-    def __init__(self, r, f: int, lambda_: float, solver="cg", cg_iters: int = 6, x_batch: int = 1,
-                 theta_batch: int = 1, fused: bool = True, chunk: int = 0, nonnegative: bool = False):
+    def __init__(self, r, f: int, x_batch: int, theta_batch: int, chunk: int):
         import torch
 
-        self.r, self.f, self.lam = r, f, float(lambda_)
-        self.solver, self.cg_iters = solver, cg_iters
-        # nonnegative: every half-iteration is update_nonneg (materialise + NNLS); solver, cg_iters and fused are unused
-        self.nonnegative = bool(nonnegative)
-        if self.nonnegative:
-            _check_nonneg_f(f)
-            self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
-        # above the tile kernels' range (f > 207) the reference's unfused data flow runs (cumf_get_hermitian + batched solver)
-        self.fused = (not self.nonnegative and bool(fused)
-                      and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver))))
+        self.r, self.f = r, f
         self.m, self.n = r.m, r.n
         self.device = r.csr_indices.device
         self.x_plans = self._plans(r.csr_indptr, r.m, x_batch, chunk)
         self.t_plans = self._plans(r.csc_indptr, r.n, theta_batch, chunk)
         self.thetaT = torch.zeros((r.n, f), dtype=torch.float32, device=self.device)
         self.XT = torch.zeros((r.m, f), dtype=torch.float32, device=self.device)
-        self._tt = None
-        self._rhs = None
 
     def _plans(self, rowptr, rows, nbatch, chunk):
         rp = rowptr.detach().cpu().numpy()
@@ -757,6 +746,51 @@ class ALSEngine(_Recommender):
         else:
             self.XT.copy_(torch.as_tensor(XT).reshape(self.m, self.f))
 
+    def update_x(self):
+        """update X from thetaT over the CSR rows (explicit feedback: als.cu:727-855)."""
+        self._half(self.x_plans, self.r.csr_indices, self.r.csr_data, self.thetaT, self.XT)
+
+    def update_theta(self):
+        """update Theta from XT over the CSC columns (explicit feedback: als.cu:857-964)."""
+        self._half(self.t_plans, self.r.csc_indices, self.r.csc_data, self.XT, self.thetaT)
+
+    def iterate(self, iters: int = 1):
+        for _ in range(iters):
+            self.update_x()
+            self.update_theta()
+
+    def close(self) -> None:
+        """Destroy the plans and hand the library's pooled scratch of this device back (up to 48 GiB of tile buffer
+        at f >= 144 that lives outside torch's caching allocator)."""
+        for p in self.x_plans + self.t_plans:
+            p.close()
+        self.x_plans, self.t_plans = [], []
+        release_scratch()
+
+
+class ALSEngine(_Engine):
+    """Explicit-feedback ALS on one GPU: the dataset of `_Engine` + the fused (or, above the tile kernels' range,
+    materialising) half-iterations.
+    """
+
+    def __init__(self, r, f: int, lambda_: float, solver="cg", cg_iters: int = 6, x_batch: int = 1,
+                 theta_batch: int = 1, fused: bool = True, chunk: int = 0, nonnegative: bool = False):
+        import torch
+
+        self.lam = float(lambda_)
+        self.solver, self.cg_iters = solver, cg_iters
+        # nonnegative: every half-iteration is update_nonneg (materialise + NNLS); solver, cg_iters and fused are unused
+        self.nonnegative = bool(nonnegative)
+        if self.nonnegative:
+            _check_nonneg_f(f)
+            self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
+        # above the tile kernels' range (f > 207) the reference's unfused data flow runs (cumf_get_hermitian + batched solver)
+        self.fused = (not self.nonnegative and bool(fused)
+                      and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver))))
+        super().__init__(r, f, x_batch, theta_batch, chunk)
+        self._tt = None
+        self._rhs = None
+
     def _half(self, plans, colidx, val, gather, update):
         import torch
 
@@ -777,14 +811,6 @@ class ALSEngine(_Recommender):
                     cg_solve(tt, xb, rhs, self.cg_iters)
                 else:
                     lu_solve(tt, rhs, xb)
-
-    def update_x(self):
-        """update X from thetaT over the CSR rows (als.cu:727-855)."""
-        self._half(self.x_plans, self.r.csr_indices, self.r.csr_data, self.thetaT, self.XT)
-
-    def update_theta(self):
-        """update Theta from XT over the CSC columns (als.cu:857-964)."""
-        self._half(self.t_plans, self.r.csc_indices, self.r.csc_data, self.XT, self.thetaT)
 
     def update_theta_with_train_sse(self):
         """update Theta AND return the train SSE of the new factors (fp64 scalar tensor) from the same kernels
@@ -809,18 +835,8 @@ class ALSEngine(_Recommender):
         return (float(tr.item() / max(r.nnz, 1)) ** 0.5, float(te.item() / max(r.nnz_test, 1)) ** 0.5)
 
     def iterate(self, iters: int = 1):
-        for _ in range(iters):
-            self.update_x()
-            self.update_theta()
+        super().iterate(iters)
         check_gram_fast()
-
-    def close(self) -> None:
-        """Destroy the plans and hand the library's pooled scratch of this device back (up to 48 GiB of tile buffer
-        at f >= 144 that lives outside torch's caching allocator)."""
-        for p in self.x_plans + self.t_plans:
-            p.close()
-        self.x_plans, self.t_plans = [], []
-        release_scratch()
 
 
 # ---------------------------------------------------------------------------------------
@@ -909,7 +925,7 @@ def implicit_loss(rowptr, colidx, val, XT, thetaT, lambda_: float, alpha: float,
     return out
 
 
-class ImplicitALSEngine(_Recommender):
+class ImplicitALSEngine(_Engine):
     """Implicit-feedback ALS on one GPU: the ratings of `r` (a `datagen.Ratings` on the device) are interaction
     strengths -- weight alpha |r|, preference r > 0 -- and every unstored entry counts as a preference of 0 with
     confidence 1.  Same shape as `ALSEngine`; each half-iteration forms G = Y^T Y of the fixed side once, before its
@@ -933,19 +949,11 @@ class ImplicitALSEngine(_Recommender):
             if not implicit_available(f, solver):
                 raise ValueError(f"implicit ALS takes even 8 <= f <= 128 with solver cg | lu and even 8 <= f <= 512 with "
                                  f"cg | cg_matfree (got f = {f}, {solver!r})")
-        self.r, self.f, self.lam, self.alpha = r, f, float(lambda_), float(alpha)
+        self.lam, self.alpha = float(lambda_), float(alpha)
         self.solver, self.cg_iters, self.reg = solver, int(cg_iters), _reg_id(reg)
-        self.m, self.n = r.m, r.n
-        self.device = r.csr_indices.device
-        self.x_plans = ALSEngine._plans(self, r.csr_indptr, r.m, x_batch, chunk)
-        self.t_plans = ALSEngine._plans(self, r.csc_indptr, r.n, theta_batch, chunk)
+        super().__init__(r, f, x_batch, theta_batch, chunk)
         self.csr_rowptr = r.csr_indptr.to(device=self.device, dtype=torch.int32).contiguous()
-        self.thetaT = torch.zeros((r.n, f), dtype=torch.float32, device=self.device)
-        self.XT = torch.zeros((r.m, f), dtype=torch.float32, device=self.device)
         self.G = torch.empty((f, f), dtype=torch.float32, device=self.device)
-
-    def init_factors(self, thetaT=None, XT=None, seed: int = 0):
-        ALSEngine.init_factors(self, thetaT, XT, seed)
 
     def _half(self, plans, colidx, val, gather, update):
         implicit_gram(gather, self.G)
@@ -957,24 +965,7 @@ class ImplicitALSEngine(_Recommender):
                 update_implicit(p, colidx, val, gather, self.G, update, self.lam, self.alpha, self.reg, self.solver,
                                 self.cg_iters)
 
-    def update_x(self):
-        self._half(self.x_plans, self.r.csr_indices, self.r.csr_data, self.thetaT, self.XT)
-
-    def update_theta(self):
-        self._half(self.t_plans, self.r.csc_indices, self.r.csc_data, self.XT, self.thetaT)
-
-    def iterate(self, iters: int = 1):
-        for _ in range(iters):
-            self.update_x()
-            self.update_theta()
-
     def loss(self) -> float:
         """The implicit objective of the current factors (fp64)."""
         return float(implicit_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.XT, self.thetaT, self.lam,
                                    self.alpha, self.reg).item())
-
-    def close(self) -> None:
-        for p in self.x_plans + self.t_plans:
-            p.close()
-        self.x_plans, self.t_plans = [], []
-        release_scratch()

@@ -6,7 +6,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "als_internal.h"
+#include "als_implicit.h"
 #include "cumf_als_capi.h"
 #include "cumf_implicit_capi.h"
 
@@ -190,14 +190,6 @@ int check_args(const char* who, const cumf_plan* p, int f, int reg_mode, int max
     return (int)hipErrorInvalidValue;
   }
   return 0;
-}
-
-template <typename T>
-int scratch(hipStream_t stream, int kind, size_t count, T** out) {
-  void* q = nullptr;
-  const int rc = scratch_get(stream, kind, (count ? count : 1) * sizeof(T), &q);
-  *out = static_cast<T*>(q);
-  return rc;
 }
 
 // The route of an implicit half-iteration, decided here only:

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "als_device.h"
-#include "als_internal.h"
+#include "als_implicit.h"
 
 namespace cumf {
 

@@ -1,4 +1,6 @@
-// als_internal.h -- declarations shared by the HIP kernels and the host side of libALS.so.
+// als_internal.h -- the core declarations shared by the HIP kernels and the host side of libALS.so: constants, kernel
+// arguments, routes, launchers, the plan and the scratch pool.  Implicit feedback, top-k, full ranking and NNLS each have a
+// header of their own (als_implicit.h, als_topk.h, als_rank.h, als_nnls.h) that only their own files include.
 #ifndef CUMF_ALS_INTERNAL_H_
 #define CUMF_ALS_INTERNAL_H_
 
@@ -275,7 +277,10 @@ hipError_t with_nb(int nb, Go&& go) {
     return nb == LO ? go(std::integral_constant<int, LO>{}) : with_nb<LO + 1, HI>(nb, go);
 }
 
-// Scratch that outlives a call (als_plan.cpp): process-wide, grow-only, one buffer per (device, stream, kind); an entry
+// Declared here, shared by the host files, but not an exported symbol of the library.
+#define CUMF_LOCAL __attribute__((visibility("hidden")))
+
+// Scratch that outlives a call (als_scratch.cpp): process-wide, grow-only, one buffer per (device, stream, kind); an entry
 // point that takes pooled scratch holds a ScratchLease until its last launch is enqueued (cumf_release_scratch waits for it).
 enum {
   kScratchTiles = 0,
@@ -303,6 +308,18 @@ enum {
   kScratchRankMetrics = 17,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
+// `count` elements of T (at least one) from the pool
+template <typename T>
+CUMF_LOCAL inline int scratch(hipStream_t stream, int kind, size_t count, T** out) {
+  void* q = nullptr;
+  const int rc = scratch_get(stream, kind, (count ? count : 1) * sizeof(T), &q);
+  *out = static_cast<T*>(q);
+  return rc;
+}
+// Bytes the pool holds for (current device, stream, kind) right now; 0: none
+CUMF_LOCAL size_t scratch_capacity(hipStream_t stream, int kind);
+// The current device's range flag of gram mode "fast" (one int, zeroed when first handed out)
+CUMF_LOCAL int fast_flag_get(int** out);
 struct ScratchLease {
   int dev = 0;
   ScratchLease();
@@ -310,204 +327,9 @@ struct ScratchLease {
   ScratchLease(const ScratchLease&) = delete;
   ScratchLease& operator=(const ScratchLease&) = delete;
 };
-// ---- Implicit feedback (als_implicit.hip kernels, als_implicit.cpp host side; include/cumf_implicit_capi.h)
-constexpr int kImpGramSlab = 1024;    // table rows per workgroup of the Gram kernel (one fp32 partial each)
-constexpr int kImpLossBlocks = 1024;  // workgroups of the loss pass (one fp64 partial each)
-constexpr int kImpRegPlain = 1;       // CUMF_IMPLICIT_REG_PLAIN (reg_u = lambda); else lambda n_u
-struct ImplicitArgs {
-  // items of the materialising kernel / the short-row CG (the plan's lists); item_dst: system index of an item's row
-  // (nullptr: row - row_begin)
-  const int* item_row;
-  const long long* item_begin;
-  const int* item_len;
-  const int* item_slot;
-  const int* item_rowlen;
-  const int* item_dst;
-  // rows cut into chunks (slot reduce); mrow_dst as item_dst
-  const int* mrow_row;
-  const int* mrow_slot0;
-  const int* mrow_nslots;
-  const int* mrow_rowlen;
-  const int* mrow_dst;
-  long long row_begin;
-  const int* colidx;
-  const float* val;
-  const float* gather;
-  const float* G;  // f x f Gram of `gather`
-  float* tt;       // systems, f x f each
-  float* rhs;      // right-hand sides (may be null)
-  float* slots;    // per-chunk partials, f x f + f each
-  float* update;   // short-row CG: warm start in, solution out
-  int f;
-  float lambda, alpha;
-  int reg_mode;
-  int cg_iters;
-};
-size_t implicit_gram_part_floats(long rows, int f);
-// G (fp32, may be null) and G64 (fp64, may be null) of a rows x f table; part: implicit_gram_part_floats floats
-hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, float* G, double* G64, hipStream_t stream);
-// systems of items [0, n_items) of a's lists, then the n_mrows chunked rows
-hipError_t launch_implicit_hermitian(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream);
-// Gram-free CG of the whole rows of items [first, first + count) (at most kShortRow entries each)
-hipError_t launch_implicit_short_cg(const ImplicitArgs& a, long first, long count, hipStream_t stream);
-hipError_t launch_implicit_copy_rows(const int* rows, long count, int f, const float* in, float* out, bool scatter,
-                                     hipStream_t stream);
-hipError_t launch_implicit_zero_rows(const int* rows, long count, int f, float* x, hipStream_t stream);
-// part: kImpLossBlocks doubles
-hipError_t launch_implicit_loss(const int* rowptr, const int* colidx, const float* val, const float* XT, const float* thetaT,
-                                long m, int f, float lambda, float alpha, int reg_mode, const double* Gx, const double* Gy,
-                                double* part, double* out, hipStream_t stream);
-// Table rows per workgroup (and fp32 partial) of the Gram: kImpGramSlab up to f = 128, more above, where a partial is f x f.
-inline long implicit_gram_slab(int f) {
-  const int FT = (f + 15) / 16;
-  return FT <= 8 ? kImpGramSlab : (long)kImpGramSlab * ((FT + 7) / 8);
-}
-// The Gram partials of a table with 128 < f <= 512 (als_implicit_free.hip; launch_implicit_gram reduces them)
-hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* part, hipStream_t stream);
-// The matrix-free CG (als_implicit_free.hip): rows are the plan's, indexed by row - row_begin; a row's stored entries are cut
-// into segments of at most kFreeSeg entries at fixed offsets from its start.
-constexpr int kFreeSeg = 2048;
-constexpr int kFreeRows = 32;  // rows per workgroup of the row pass
-struct ImplicitFreeArgs {
-  const int* seg_row;            // nseg: row of each segment
-  const long long* seg_begin;    // ... its first entry (index into colidx / val)
-  const int* seg_len;
-  const int* row_seg0;           // rows: first segment of each row (its segments are consecutive)
-  const int* row_nseg;
-  const int* row_len;            // stored entries of the row (0: x = 0)
-  long long rows, nseg;
-  const int* colidx;
-  const float* val;
-  const float* gather;
-  const float* G;
-  float* x;      // update + row_begin * f: warm start in, solution out
-  float* r;      // rows x f residuals
-  float* p;      // rows x f search directions
-  float* part;   // nseg x f: T^T (w o T v) of each segment
-  float* bpart;  // nseg x f: the segment's part of b (first pass)
-  float* rs;     // rows: r.r
-  int* done;     // rows: 1 once the row's CG has ended (zeroed before the first pass)
-  int f;
-  float lambda, alpha;
-  int reg_mode;
-};
-// step 0: the sparse pass with v = x (and b), then r = b - A x, p = r; step k >= 1: CG step k with A p.  step == cg_iters: the
-// last pass.
-hipError_t launch_implicit_free_pass(const ImplicitFreeArgs& a, int step, int cg_iters, hipStream_t stream);
-// Work lists of the implicit-feedback half-iterations, built on a plan at first use (als_implicit.cpp).
+// Work lists of the implicit-feedback half-iterations, built on a plan at first use and freed with it (als_implicit.cpp).
 struct ImplicitLists;
 void free_implicit_lists(ImplicitLists* lists);
-
-// ---- Top-k recommendation and ranking metrics (als_topk.hip kernels, als_topk.cpp host side; include/cumf_topk_capi.h)
-constexpr int kTopkThreads = 256;         // four waves
-constexpr int kTopkQW = 32;               // queries per wave (two 16-row MFMA tiles)
-constexpr int kTopkQB = 4 * kTopkQW;      // queries per workgroup
-constexpr int kTopkNC = 64;               // candidates per LDS block (four 16-column tiles; one 64-bit exclusion mask)
-constexpr int kTopkJC = 128;              // features per LDS chunk
-constexpr int kTopkPitch = kTopkJC + 4;   // LDS row pitch: the 16 rows one k-group reads start 4 banks apart
-constexpr int kTopkBuf = 128;             // survivor buffer per query (merged when above kTopkBuf - kTopkNC)
-constexpr int kTopkMaxK = 128;
-constexpr int kTopkMaxF = 512;
-struct TopkArgs {
-  const float* Q;
-  long long rows;
-  const float* C;
-  long long ncand;
-  int f, k;
-  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
-  int rowptr64;
-  const int* excl_colidx;
-  int vec;                  // C rows may be read as float4 (f % 4 == 0, 16-byte aligned)
-  int nslab;
-  long long slab_len;       // candidates per slab, a multiple of kTopkNC
-  long long n_items;        // query blocks x slabs
-  unsigned long long* work; // per workgroup: kTopkQB x (k + kTopkBuf) keys
-  unsigned long long* part; // nslab > 1: nslab x rows x k keys
-  int* ids;                 // nslab == 1: the result
-  float* scores;
-};
-int topk_score_occupancy(bool multi);  // workgroups per CU of the score kernel
-hipError_t launch_topk_score(const TopkArgs& a, long long grid, hipStream_t stream);
-hipError_t launch_topk_merge(const unsigned long long* part, long long rows, int k, int nslab, int* ids, float* scores,
-                             hipStream_t stream);
-// part: 4 x rows doubles; out: (count, precision, recall, ndcg)
-hipError_t launch_topk_metrics(const int* ids, long long rows, int k, const void* rowptr, int rowptr64, const int* colidx,
-                               const float* val, double* part, double* out, hipStream_t stream);
-
-// How a scoring kernel cuts the work, decided here only: query blocks of kTopkQB x slabs of the candidates, on a persistent
-// grid of at most one workgroup per resident slot.  A query block alone takes all candidates (one slab) when there are at
-// least two blocks per slot; fewer blocks (few queries, e.g. the items x users side of Netflix) split the candidates into
-// slabs until there are, but no slab below kTopkMinSlab candidates.  The result does not depend on the cut.
-constexpr long long kTopkMinSlab = 16 * kTopkNC;  // candidates per slab at least: the per-slab set-up stays a small part
-struct TopkCut {
-  int nslab;
-  long long slab_len;
-  long long n_items;
-  long long grid;
-};
-inline TopkCut topk_cut(long long rows, long long ncand, int cus, int wgs_per_cu) {
-  const long long qblocks = (rows + kTopkQB - 1) / kTopkQB;
-  const long long slots = (long long)cus * wgs_per_cu;
-  long long nslab = 1;
-  if (qblocks < 2 * slots) nslab = (2 * slots + qblocks - 1) / qblocks;
-  nslab = std::min(nslab, std::max(1LL, (ncand + kTopkMinSlab - 1) / kTopkMinSlab));
-  long long slab_len = (ncand + nslab - 1) / nslab;
-  slab_len = std::max((long long)kTopkNC, (slab_len + kTopkNC - 1) / kTopkNC * kTopkNC);
-  nslab = std::max(1LL, (ncand + slab_len - 1) / slab_len);
-  const long long items = qblocks * nslab;
-  return TopkCut{(int)nslab, slab_len, items, std::min(items, slots)};
-}
-
-// ---- Full ranking: held-out ranks and their metrics (als_rank.hip kernels, als_rank.cpp host side; include/cumf_rank_capi.h)
-constexpr int kRankPoolW = 768;            // held-out keys (and buckets) a wave keeps in LDS for its kTopkQW queries
-constexpr int kRankPool = 4 * kRankPoolW;  // ... per workgroup; a wave whose queries have more works on the global arrays
-constexpr int kRankMaxK = 16;              // cut-offs per cumf_rank_metrics call
-constexpr int kRankCols = 7;               // per-query metric columns in front of the 3 per cut-off
-struct RankArgs {
-  const float* Q;
-  long long rows;
-  const float* C;
-  long long ncand;
-  int f;
-  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
-  int rowptr64;
-  const int* excl_colidx;
-  int vec;                  // C rows may be read as float4 (f % 4 == 0, 16-byte aligned)
-  const void* test_rowptr;  // rows + 1 entries, int32 or int64 (test_rowptr64)
-  int test_rowptr64;
-  const int* test_colidx;
-  long long n_test;         // entries of test_colidx (and of keys, hist, ranks)
-  int nslab;
-  long long slab_len;       // candidates per slab, a multiple of kTopkNC
-  long long n_items;        // query blocks x slabs
-  unsigned long long* keys; // per held-out entry: its key (0: not eligible), sorted in descending order within each row
-  int* hist;                // per row: bucket b = eligible candidates below exactly b of the row's valid keys
-  int* nvalid;              // per query: its non-zero keys
-  int* ranks;
-  int* n_eligible;
-};
-struct RankKs {
-  int n;
-  int k[kRankMaxK];
-};
-int rank_count_occupancy(bool multi);  // workgroups per CU of the count kernel
-// keys + ranks = -1 of the entries that are not eligible, the sort of each row, nvalid; hist and n_eligible zeroed
-hipError_t launch_rank_thresholds(const RankArgs& a, hipStream_t stream);
-hipError_t launch_rank_count(const RankArgs& a, long long grid, hipStream_t stream);
-hipError_t launch_rank_finish(const RankArgs& a, hipStream_t stream);
-// keys: n_test; part: (kRankCols + 3 ks.n) x rows doubles; out: 6 + 3 ks.n doubles
-hipError_t launch_rank_metrics(const int* ranks, const int* n_eligible, long long rows, const void* rowptr, int rowptr64,
-                               const float* val, long long n_test, const RankKs& ks, unsigned long long* keys, double* part,
-                               double* out, hipStream_t stream);
-
-// ---- Non-negative least squares (als_nnls.hip kernel, als_nnls.cpp host side; include/cumf_nnls_capi.h)
-constexpr int kNnlsMaxF = 128;
-constexpr int kNnlsMaxNB = nb_for_f(kNnlsMaxF);  // 9
-constexpr int kNnlsGrid = 2048;                  // workgroups of the grid-stride launch
-constexpr int kNnlsDefaultItersBase = 16;        // max_iters = 0: 16 + 2 f steps per system
-// cap: passive-set steps per system; stats (may be null): [0] += systems not converged, [1] += factorisations
-hipError_t launch_nnls(const float* A, const float* b, float* x, long batch, int f, int cap, long long* stats,
-                       hipStream_t stream);
 
 }  // namespace cumf
 
@@ -545,9 +367,10 @@ struct cumf_plan {
 
 namespace cumf {
 
-// The plan's rows without stored entries (absolute row ids, device array) from the lists of als_implicit.cpp, built on
-// first use.
-int plan_empty_rows(cumf_plan* p, const int** rows, long* count);
+// What the entry points take from a plan (als_plan.cpp).  plan_lists: its work lists for launch_half_iteration; need_tiles:
+// with the dense-slot tile buffer from the pool (Route::whole == kSolveTileBuffer).  plan_facts: what the route depends on.
+CUMF_LOCAL int plan_lists(const cumf_plan* p, PlanLists* out, hipStream_t stream, bool need_tiles);
+CUMF_LOCAL PlanFacts plan_facts(const cumf_plan* p);
 
 // One launch: the dynamic-LDS opt-in above 64 KB, the launch, its error.  launch_item_kernel (NOTE): a Gram(+solve)
 // kernel, also recorded for cumf_last_kernel_name.

@@ -4,7 +4,8 @@
 
 #include <cstdio>
 
-#include "als_internal.h"
+#include "als_implicit.h"
+#include "als_nnls.h"
 #include "cumf_als_capi.h"
 #include "cumf_implicit_capi.h"
 #include "cumf_nnls_capi.h"
@@ -16,14 +17,6 @@ namespace {
 bool nnls_f_ok(int f) { return f >= 1 && f <= kNnlsMaxF; }
 bool route_f_ok(int f) { return f >= 8 && f <= kNnlsMaxF && (f % 2) == 0; }
 int cap_of(int f, int max_iters) { return max_iters > 0 ? max_iters : kNnlsDefaultItersBase + 2 * f; }
-
-template <typename T>
-int scratch(hipStream_t stream, int kind, size_t count, T** out) {
-  void* q = nullptr;
-  const int rc = scratch_get(stream, kind, (count ? count : 1) * sizeof(T), &q);
-  *out = static_cast<T*>(q);
-  return rc;
-}
 
 int check_route(const char* who, const cumf_plan_t* p, int f, int max_iters) {
   if (!p || f != p->f || !route_f_ok(f) || max_iters < 0) {

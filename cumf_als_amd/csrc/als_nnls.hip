@@ -21,7 +21,7 @@
 
 #include <climits>
 
-#include "als_internal.h"
+#include "als_nnls.h"
 #include "als_device.h"
 #include "als_lu_reg.h"
 

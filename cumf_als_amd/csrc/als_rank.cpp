@@ -5,7 +5,7 @@
 #include <algorithm>
 #include <cstdio>
 
-#include "als_internal.h"
+#include "als_rank.h"
 #include "cumf_rank_capi.h"
 
 using namespace cumf;
@@ -13,14 +13,6 @@ using namespace cumf;
 namespace {
 
 bool rank_ok(int f) { return f >= 1 && f <= kTopkMaxF; }
-
-template <typename T>
-int scratch(hipStream_t stream, int kind, size_t count, T** out) {
-  void* q = nullptr;
-  const int rc = scratch_get(stream, kind, (count ? count : 1) * sizeof(T), &q);
-  *out = static_cast<T*>(q);
-  return rc;
-}
 
 }  // namespace
 

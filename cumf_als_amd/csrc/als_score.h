@@ -6,7 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "als_internal.h"
+#include "als_topk.h"
 
 namespace cumf {
 

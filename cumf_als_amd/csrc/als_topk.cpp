@@ -1,11 +1,11 @@
 // als_topk.cpp -- host side of top-k recommendation and ranking metrics (include/cumf_topk_capi.h): argument checks, the slab
-// cut (topk_cut, als_internal.h), scratch, launches.  Kernels: als_topk.hip.
+// cut (topk_cut, als_topk.h), scratch, launches.  Kernels: als_topk.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 
-#include "als_internal.h"
+#include "als_topk.h"
 #include "cumf_topk_capi.h"
 
 using namespace cumf;
@@ -13,14 +13,6 @@ using namespace cumf;
 namespace {
 
 bool topk_ok(int f, int k) { return f >= 1 && f <= kTopkMaxF && k >= 1 && k <= kTopkMaxK; }
-
-template <typename T>
-int scratch(hipStream_t stream, int kind, size_t count, T** out) {
-  void* q = nullptr;
-  const int rc = scratch_get(stream, kind, (count ? count : 1) * sizeof(T), &q);
-  *out = static_cast<T*>(q);
-  return rc;
-}
 
 }  // namespace
 

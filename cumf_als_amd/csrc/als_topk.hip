@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "als_device.h"
-#include "als_internal.h"
+#include "als_topk.h"
 #include "als_score.h"
 
 namespace cumf {

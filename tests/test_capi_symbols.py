@@ -7,19 +7,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared_c_symbols(header="cumf_als_capi.h"):
+    """{symbol: number of parameters} of every function a header of include/ declares."""
     text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(cumf_[A-Za-z0-9_]+)\s*\(", text)))
+    text = re.sub(r"//[^\n]*", "", text)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
+            for name, params in re.findall(r"\b(cumf_[A-Za-z0-9_]+)\s*\(([^()]*)\)", text)}
 
 
 def test_header_symbols_are_exported(alslib):
+    """Each of the six headers against its table in lib.py: the same symbols, the same number of parameters, and the
+    library exports them all."""
     from cumf_als_amd import lib
 
-    declared = _declared_c_symbols()
-    assert set(declared) == set(lib.C_SYMBOLS), (declared, lib.C_SYMBOLS)
-    declared_dist = _declared_c_symbols("cumf_dist_capi.h")   # the multi-GPU half-iterations (als_dist.cpp)
-    assert set(declared_dist) == set(lib.DIST_SYMBOLS), (declared_dist, lib.DIST_SYMBOLS)
-    for s in declared + declared_dist + lib.CXX_SYMBOLS:
+    assert sorted(lib.ABI_BY_HEADER) == sorted(h for h in os.listdir(os.path.join(ROOT, "include")) if h.startswith("cumf_"))
+    for header, table in lib.ABI_BY_HEADER.items():
+        declared = _declared_c_symbols(header)
+        assert declared and set(declared) == set(table), (header, sorted(set(declared) ^ set(table)))
+        for s, n_params in declared.items():
+            assert len(table[s][1]) == n_params, (header, s, n_params, len(table[s][1]))
+            assert hasattr(alslib, s), s
+    for s in lib.CXX_SYMBOLS:
         assert hasattr(alslib, s), s
     assert alslib.cumf_als_arch() == b"gfx950"
 

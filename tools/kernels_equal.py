@@ -4,8 +4,9 @@
     python tools/kernels_equal.py DIR_A DIR_B              every *.o directly in each directory
 
 Each side is the union of the kernels of its objects, keyed by symbol, so kernels may move between objects (a kernel that
-two objects of one side carry in different versions is reported).  Point it at csrc/*.o, not at libALS.so: the linked
-library carries one offload bundle per translation unit back to back, and one --unbundle may see only the first.  Per
+two objects of one side carry in different versions is reported; the profiling build's *_ablate.o objects are a set of
+their own, compared with the other side's).  Point it at csrc/*.o, not at libALS.so: the linked library carries one
+offload bundle per translation unit back to back, and one --unbundle may see only the first.  Per
 kernel it compares the instructions (llvm-objdump, with branch-target labels, trailing comments and the PC-relative
 literal after each s_getpc_b64 normalised: that offset to a global such as g_wave_zeros moves when the kernel order
 changes) and the register / LDS / scratch / kernarg metadata (llvm-readelf --notes).  Kernels present on one side only are
@@ -81,7 +82,10 @@ def side(arg, diffs):
     """{symbol: (instructions, metadata)} over every object of one side."""
     out = {}
     for obj in objects(arg):
+        # the profiling build's objects (*_ablate.o) carry kernels of the product's names compiled with other switches
+        tag = " [ablate]" if os.path.basename(obj).endswith("_ablate.o") else ""
         for k, v in kernels(obj).items():
+            k += tag
             if k in out and out[k] != v:
                 diffs.append(f"two versions of {k} in {arg}")
             out[k] = v
