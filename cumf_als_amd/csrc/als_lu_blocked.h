@@ -1,4 +1,4 @@
-// als_lu_blocked.h -- the pieces of the blocked elimination (round 4: lu_wave_blocked, als_wave.hip): the exact bf16x3 split
+// als_lu_blocked.h -- the pieces of the blocked elimination (round 4: lu_wave_blocked, als_wave_solve.h): the exact bf16x3 split
 // (also the Gram stage's and the pre-split kernel's), the preparation of one four-pivot panel on the accumulators of ONE wave
 // (DPP quad broadcasts + ds_bpermute, no barrier), the rank-16 bf16 MFMA.  (Round 5 shared them with a row-owning workgroup
 // LU of the large systems that was built, was correct and was slower: it lives as profiles/r05/lu_rows_experiment.patch,
