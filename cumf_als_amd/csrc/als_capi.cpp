@@ -156,8 +156,8 @@ int update_fused_impl(const cumf_plan_t* p, const int* colidx, const float* val,
   }
   if (!cumf_fused_available(f, solver)) {
     fprintf(stderr, "cumf_als_update_fused: f = %d with this solver needs the materialising path "
-                    "(cumf_get_hermitian + cumf_*_solve_batched): the fused CG holds the full system "
-                    "in LDS (f <= 128), the fused LU its packed upper triangle (f <= 200)\n", f);
+                    "(cumf_get_hermitian + cumf_*_solve_batched): the fused LU serves even f <= %d, the fused CG "
+                    "too except in gram mode exact (the full system in LDS, f <= %d)\n", f, kMaxF, kVecLd);
     return (int)hipErrorInvalidValue;
   }
   ScratchLease lease;  // pooled tile buffer / pre-split table stay ours until the last launch below is enqueued
@@ -274,8 +274,14 @@ extern "C" int cumf_lu_solve_batched(const float* A, const float* b, float* x, l
   }
   if (f > 200) {
     // above the LDS-resident solvers: the elimination in global memory, in the operation order of the unpivoted Doolittle LU +
-    // getrs (als_generic.hip).  A is overwritten with the factors, as cublasSgetrfBatched overwrites it (als.cu:77).
-    CUMF_HIP_CHECK(launch_lu_global(const_cast<float*>(A), b, x, batch, f, static_cast<hipStream_t>(stream)));
+    // getrs (als_generic.hip).  cublasSgetrfBatched overwrites A with the factors (als.cu:77); here they are formed in a
+    // pooled copy of the batch (batch x f x f floats), so that A stays intact as the header promises for every f.
+    if (batch <= 0) return 0;
+    ScratchLease lease;
+    float* work = nullptr;
+    const int rc = scratch(static_cast<hipStream_t>(stream), kScratchLuWork, (size_t)batch * f * f, &work);
+    if (rc) return rc;
+    CUMF_HIP_CHECK(launch_lu_global(A, work, b, x, batch, f, static_cast<hipStream_t>(stream)));
     return 0;
   }
   // CUMF_ALS_LU_EXACT=1: the LDS-resident elimination in the oracle's exact operation order

@@ -424,7 +424,7 @@ extern "C" int cumf_dist_reduce_update_theta(cumf_dist_reduce_t* r, const cumf_p
         DIST_CHECK(cumf_cg_solve_batched(r->my_tt, r->x[slot], r->mine_rhs[slot], cnt, f, cg_iters, stream));
       else
         DIST_CHECK(cumf_lu_solve_batched(r->my_tt, r->mine_rhs[slot], r->x[slot], cnt, f, stream));
-      if (sse_terms)  // the solvers leave A and b intact (f <= 200)
+      if (sse_terms)  // the solvers leave A and b intact (cumf_als_capi.h)
         DIST_CHECK(cumf_quadratic_sse_terms(r->my_tt, r->mine_rhs[slot], r->x[slot], reg_all + off + lo, cnt, f,
                                             sse_terms, stream));
     }

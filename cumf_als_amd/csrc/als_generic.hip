@@ -10,7 +10,8 @@
 //                         written to both triangles from the upper entry, lambda * n_u on the diagonal (als.cu:545-557);
 //   lu_global_kernel      unpivoted Doolittle LU + the two triangular solves (cublasSgetrfBatched(Pivot = NULL) +
 //                         cublasSgetrsBatched, als.cu:77,98 / 146,166) in global memory, the elimination's (i, j) updates
-//                         spread over the workgroup, every element's own operation sequence unchanged.
+//                         spread over the workgroup, every element's own operation sequence unchanged.  The elimination
+//                         runs on a work copy of each system: the caller's A is only read.
 // CG above f = 207 is cg_global_kernel (als_kernels.hip).
 #include <hip/hip_runtime.h>
 
@@ -99,14 +100,18 @@ __global__ __launch_bounds__(kGenThreads) void gram_generic_kernel(const KernelA
   }
 }
 
-// One workgroup per system; A (f x f, row-major, overwritten with the factors) and b -> x, all in global memory.
-__global__ __launch_bounds__(kGenThreads) void lu_global_kernel(float* __restrict__ A, const float* __restrict__ b,
-                                                                float* __restrict__ x, int f) {
+// One workgroup per system; A (f x f, row-major, read only) and b -> x, all in global memory.  The workgroup copies its
+// system into its f x f slice of `work` and eliminates there: `work` ends up holding the factors, A stays as it was.
+__global__ __launch_bounds__(kGenThreads) void lu_global_kernel(const float* __restrict__ A, float* __restrict__ work,
+                                                                const float* __restrict__ b, float* __restrict__ x, int f) {
   extern __shared__ __attribute__((aligned(16))) float y[];  // f: the running right-hand side
-  float* As = A + (size_t)blockIdx.x * f * f;
+  const float* Ain = A + (size_t)blockIdx.x * f * f;
+  float* As = work + (size_t)blockIdx.x * f * f;
   const float* bs = b + (size_t)blockIdx.x * f;
   float* xs = x + (size_t)blockIdx.x * f;
   const int tid = threadIdx.x;
+  for (int e = tid; e < f * f; e += kGenThreads) As[e] = Ain[e];
+  __syncthreads();
   for (int k = 0; k < f; ++k) {
     const float piv = As[(size_t)k * f + k];
     // multipliers of column k (rows i > k), then the trailing update, each (i, j) by one thread
@@ -147,9 +152,11 @@ hipError_t launch_gram_generic(const KernelArgs& a, long n_items, hipStream_t st
   return launch_kernel(gram_generic_kernel, dim3((unsigned)n_items), dim3(kGenThreads), lds, stream, a);
 }
 
-hipError_t launch_lu_global(float* A, const float* b, float* x, long batch, int f, hipStream_t stream) {
+hipError_t launch_lu_global(const float* A, float* work, const float* b, float* x, long batch, int f, hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
-  return launch_kernel(lu_global_kernel, dim3((unsigned)batch), dim3(kGenThreads), (size_t)f * sizeof(float), stream, A, b, x, f);
+  if (!work) return hipErrorInvalidValue;
+  return launch_kernel(lu_global_kernel, dim3((unsigned)batch), dim3(kGenThreads), (size_t)f * sizeof(float), stream, A, work, b,
+                       x, f);
 }
 
 }  // namespace cumf

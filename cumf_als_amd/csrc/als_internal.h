@@ -205,9 +205,10 @@ hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, 
 // `packed` receives the mirrored full matrices
 hipError_t launch_presplit(const float* src, unsigned* dst, size_t n, int* flag, hipStream_t stream);
 // f > kMaxF (als_generic.hip): the fp32 f x f Gram batch + right-hand sides of the plan's items (whole rows), and the batched
-// unpivoted LU in global memory (A is overwritten with the factors, as cublasSgetrfBatched does)
+// unpivoted LU in global memory (cumf_lu_solve_batched above f = 200): A is only read; the factors are formed in `work`,
+// batch x f x f floats of the caller's (cublasSgetrfBatched overwrites A instead)
 hipError_t launch_gram_generic(const KernelArgs& a, long n_items, hipStream_t stream);
-hipError_t launch_lu_global(float* A, const float* b, float* x, long batch, int f, hipStream_t stream);
+hipError_t launch_lu_global(const float* A, float* work, const float* b, float* x, long batch, int f, hipStream_t stream);
 // kArithPre: which (f, NB) have kernels on the pre-split bf16x3 table (als_wave.hip: CUMF_WAVE_PRE, presplit_shape_ok), the
 // table's row pitch in bytes, and the kernel that writes it
 // One-wave kernels (NB = 5, 7): strip of f % 16 in {0, 4} features; two-wave kernels (NB = 8 .. 13): f % 16 in {0, 4, 8}.
@@ -306,6 +307,8 @@ enum {
   kScratchRankHist = 15,
   kScratchRankValid = 16,
   kScratchRankMetrics = 17,
+  // cumf_lu_solve_batched above f = 200: the batch the elimination in global memory factors in place of the caller's A
+  kScratchLuWork = 18,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 // `count` elements of T (at least one) from the pool
