@@ -1,5 +1,5 @@
-// als_device.h -- device helpers shared by als_kernels.hip (workgroup-per-item kernels) and
-// als_wave.hip (wave-per-item kernels): tile enumeration, compile-time loops, DPP reductions, the
+// als_device.h -- device helpers shared by the workgroup kernels (als_kernels.hip, als_wg_*.h) and the wave kernels
+// (als_wave.hip, als_wave_*.h): tile enumeration, compile-time loops, DPP reductions, the
 // packed upper-triangular row store of the LU paths and its back substitution.
 #ifndef CUMF_ALS_DEVICE_H_
 #define CUMF_ALS_DEVICE_H_

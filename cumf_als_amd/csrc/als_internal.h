@@ -41,7 +41,7 @@ __host__ __device__ constexpr int solve_ldg(int f, int mode) { return mode == kM
 __host__ __device__ constexpr size_t solve_g_floats(int f, int mode) {
   return ((size_t)f * solve_ldg(f, mode) + 3) & ~(size_t)3;
 }
-// Register LU (fast path): packed upper-triangular row store (als_kernels.hip: lu_row_off) + f
+// Register LU (fast path): packed upper-triangular row store (als_device.h: lu_row_off) + f
 // pivot reciprocals.  f = 100: 29 520 B, below the 32 256 B of the stage buffers it aliases
 // -> 5 workgroups per CU.
 __host__ __device__ constexpr size_t lu_packed_floats(int nb) { return (size_t)256 * nb * (nb + 1) / 2 + 16 * nb; }
@@ -248,7 +248,8 @@ hipError_t launch_cg_global(const float* A, const float* b, float* x, long batch
 
 // ---- Per-NB entry points: function templates of the kernel files, each explicitly instantiated in the translation unit
 // of its NB only (Makefile: als_kernels.hip once per CUMF_NB_SLICE, als_wave.hip once per CUMF_WAVE_NB and part).
-// als_kernels.hip, NB = 1 .. kMaxNB; slice_solve also NB = 0: the oracle-order LU of CUMF_ALS_LU_EXACT
+// als_kernels.hip, NB = 1 .. kMaxNB; slice_solve also NB = 0: the oracle-order LU of CUMF_ALS_LU_EXACT.  slice_reduce_only: the
+// solver of chunked rows (or of the dense slots of the tile buffer) on its own, behind the wave kernels' items
 template <int NB>
 hipError_t slice_half_iteration(const KernelArgs& a, int mode, long n_items, long n_mrows, hipStream_t stream);
 template <int NB>
@@ -256,8 +257,6 @@ hipError_t slice_solve(const float* A, const float* b, float* x, long batch, int
                        hipStream_t stream);
 template <int NB>
 hipError_t slice_reduce_only(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream);
-template <int NB>
-hipError_t slice_batched(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream);
 // als_wave.hip, NB = 2 .. kMaxNB; wave_lu_launch: NB <= kMaxWaveNB (part 1); wave_cg_hist: profiling build only
 // whole: every item of the launch is a whole row (the LU instance without the dump exit)
 template <int NB>

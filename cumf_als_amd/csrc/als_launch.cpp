@@ -1,5 +1,6 @@
-// als_launch.cpp -- carries out a route: the per-NB entry points of the kernel files (als_internal.h) for the run-time
-// feature-block count, the standalone batched solvers, and the optional HIP-event timing of the launch sequences.
+// als_launch.cpp -- carries out a route (workgroup, one-wave or two-wave path): which per-NB entry points of the kernel files
+// (als_internal.h) run on which item lists, for the run-time feature-block count; the standalone batched solvers; and the
+// optional HIP-event timing of the launch sequences.
 // Host only: every kernel is launched by the kernel files' own launchers.
 #include <atomic>
 #include <mutex>
@@ -81,20 +82,32 @@ void note_item_kernel(const void* host_function) { g_last_item_kernel.store(host
 const void* last_item_kernel() { return g_last_item_kernel.load(std::memory_order_relaxed); }
 
 // ---- Half-iteration
-// the wave kernels of one launch, by NB (als_wave.hip)
+// the wave kernels of one launch, by NB (als_wave.hip): one wave per item up to kMaxWaveNB, two above
 static hipError_t wave_items(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream) {
-  return with_nb<2, kMaxWaveNB>(nb_for_f(a.f), [&](auto nb) { return wave_item_launch<nb>(a, mode, r, whole, n_items, stream); });
+  return with_nb<2, kMaxNB>(nb_for_f(a.f), [&](auto nb) { return wave_item_launch<nb>(a, mode, r, whole, n_items, stream); });
+}
+// the solver of the chunked rows on its own (als_kernels.hip)
+static hipError_t reduce_rows(const KernelArgs& a, int mode, const Route& r, long n_mrows, hipStream_t stream) {
+  return with_nb<1, kMaxNB>(nb_for_f(a.f), [&](auto nb) { return slice_reduce_only<nb>(a, mode, r, n_mrows, stream); });
+}
+
+// The item lists of a launch: the plan's whole rows from row w0 of the w list on (no slots: nothing is dumped by slot) ...
+static KernelArgs whole_row_items(KernelArgs a, const PlanLists& L, long w0 = 0) {
+  a.item_row = L.w_row + w0, a.item_begin = L.w_begin + w0, a.item_len = L.w_len + w0;
+  a.item_slot = nullptr, a.item_rowlen = L.w_rowlen + w0;
+  return a;
+}
+// ... or its chunk items, each with its slot of the plan's partial tiles
+static KernelArgs chunk_items(KernelArgs a, const PlanLists& L) {
+  a.item_row = L.c_row, a.item_begin = L.c_begin, a.item_len = L.c_len;
+  a.item_slot = L.c_slot, a.item_rowlen = L.c_rowlen;
+  return a;
 }
 
 // One-wave path: the items of the plan (Route::n_short, Route::chunk_first), then launch_half_iteration's reduce phase
 static hipError_t one_wave_items(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
-  KernelArgs aw = a;
-  long n_items = L.n_items;
-  if (r.chunk_first) {
-    aw.item_row = L.w_row, aw.item_begin = L.w_begin, aw.item_len = L.w_len;
-    aw.item_slot = nullptr, aw.item_rowlen = L.w_rowlen;
-    n_items = L.n_witems;
-  }
+  const KernelArgs aw = r.chunk_first ? whole_row_items(a, L) : a;
+  long n_items = r.chunk_first ? L.n_witems : L.n_items;
   if (r.n_short > 0) {  // the last items; first: the tail of the long items then fills in behind it
     n_items -= r.n_short;
     KernelArgs as = aw;
@@ -103,13 +116,47 @@ static hipError_t one_wave_items(const KernelArgs& a, int mode, const Route& r, 
     if (e != hipSuccess) return e;
   }
   if (r.chunk_first) {
-    KernelArgs ac = a;
-    ac.item_row = L.c_row, ac.item_begin = L.c_begin, ac.item_len = L.c_len;
-    ac.item_slot = L.c_slot, ac.item_rowlen = L.c_rowlen;
-    hipError_t e = wave_items(ac, mode, r, false, L.n_citems, stream);
+    hipError_t e = wave_items(chunk_items(a, L), mode, r, false, L.n_citems, stream);
     if (e != hipSuccess) return e;
   }
   return wave_items(aw, mode, r, r.chunk_first || L.n_mrows == 0, n_items, stream);
+}
+
+// Two-wave path (f >= 112): the Gram of every row is dumped as accumulator tiles (two waves per item,
+// als_wave_multi_kernel) and a solver kernel (single-wave LU up to NB = 10, the 4-wave lu_solve_mfma
+// above that, wave-level CG on the tiles) picks them up -- the reference's own data flow ("Gram batch
+// in device memory, separate solver", als.cu:782-831), with tiles instead of full f x f matrices and
+// in batches of the pooled tile buffer (als_plan.cpp: up to 48 GiB, usually ONE batch).
+static hipError_t two_wave_items(const KernelArgs& a0, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  // 1. chunked rows: their items write the plan's slots, the reduce kernel sums and solves
+  if (L.n_citems > 0) {
+    e = wave_items(chunk_items(a0, L), kModeLU, r, false, L.n_citems, stream);  // every item has a slot: nothing is solved in place
+    if (e != hipSuccess) return e;
+    e = reduce_rows(a0, mode, r, L.n_mrows, stream);
+    if (e != hipSuccess) return e;
+  }
+  // 2. whole rows: solved by the two waves that formed the Gram, in one launch, or through the tile buffer
+  if (r.whole == kSolveInKernel) {
+    if (L.n_witems <= 0) return hipSuccess;
+    KernelArgs a = whole_row_items(a0, L);
+    a.dense_slots = 0;
+    return wave_items(a, mode, r, false, L.n_witems, stream);
+  }
+  // large LU / materialise (cumf_get_hermitian): in batches of part2_rows dense slots
+  for (long w0 = 0; w0 < L.n_witems; w0 += L.part2_rows) {
+    const long cnt = L.n_witems - w0 < L.part2_rows ? L.n_witems - w0 : L.part2_rows;
+    KernelArgs a = whole_row_items(a0, L, w0);
+    a.dense_slots = 1;
+    a.part = L.part2;
+    a.mrow_row = L.w_row + w0;
+    a.mrow_rowlen = L.w_rowlen + w0;
+    e = wave_items(a, kModeLU, r, false, cnt, stream);
+    if (e != hipSuccess) return e;
+    e = reduce_rows(a, mode, r, cnt, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
@@ -124,7 +171,7 @@ hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, 
   hipError_t e = hipErrorInvalidValue;
   switch (r.path) {
     case kPathTwoWave:
-      e = with_nb<kMaxWaveNB + 1, kMaxNB>(nb, [&](auto n) { return slice_batched<n>(a, mode, r, L, stream); });
+      e = nb > kMaxWaveNB ? two_wave_items(a, mode, r, L, stream) : hipErrorInvalidValue;
       break;
     case kPathOneWave: e = one_wave_items(a, mode, r, L, stream); break;
     case kPathWorkgroup:
@@ -134,10 +181,9 @@ hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, 
   }
   if (t) (void)hipEventRecord(t->ev[1], stream);
   if (e == hipSuccess && r.path != kPathTwoWave && L.n_mrows > 0) {
-    e = with_nb<1, kMaxNB>(nb, [&](auto n) {
-      return r.path == kPathOneWave ? slice_reduce_only<n>(a, mode, r, L.n_mrows, stream)
-                                    : slice_half_iteration<n>(a, mode, 0, L.n_mrows, stream);
-    });
+    e = r.path == kPathOneWave
+            ? reduce_rows(a, mode, r, L.n_mrows, stream)
+            : with_nb<1, kMaxNB>(nb, [&](auto n) { return slice_half_iteration<n>(a, mode, 0, L.n_mrows, stream); });
   }
   if (t) (void)hipEventRecord(t->ev[2], stream);
   return e;

@@ -1,4 +1,4 @@
-// Shared by als_kernels.hip (four wave roles per workgroup) and als_wave.hip (two waves per item):
+// Shared by the workgroup kernels (als_kernels.hip: finish_row, four wave roles per workgroup) and als_wave.hip (two waves per item):
 // the LU on MFMA accumulator tiles dealt round-robin to NW wave roles.
 #pragma once
 #include "als_device.h"
@@ -21,7 +21,7 @@ using LuAcc = f32x4[LuGeo<NB, NW>::TPW];  // the accumulator tiles of one wave r
 // ----------------------------------------------------------------------------------
 // LU directly on the MFMA accumulators (the fused kernels' LU path).
 //
-// After the Gram pass wave role W of NW (4 in the workgroup kernels of als_kernels.hip, 2 in the
+// After the Gram pass wave role W of NW (4 in the workgroup kernels of als_kernels.hip, whose Geo<NB> of als_wg_tiles.h deals the same tiles; 2 in the
 // two-wave kernel of als_wave.hip) holds the tiles t = W + NW s of the upper triangle of [A | b] in
 // the 16x16x4 C/D layout (lane (kk, c) = (l >> 4, l & 15), register r: element
 // (16 I + 4 kk + r, 16 J + c)).  The elimination keeps them there and applies FOUR pivots per

@@ -465,7 +465,7 @@ def test_gather_table_guard(alslib):
 
 
 @pytest.mark.parametrize("gram_mode", ["exact", "auto"], indirect=True)
-@pytest.mark.parametrize("f,chunk", [(100, 32), (100, 64), (20, 32), (64, 96)])
+@pytest.mark.parametrize("f,chunk", [(100, 32), (100, 64), (20, 32), (64, 96), (128, 64), (160, 32)])
 def test_gram_chunked_rows(oracle, alslib, gram_mode, f, chunk):
     _need_gpu()
     from cumf_als_amd import als

@@ -1,10 +1,12 @@
 """Are two builds of the library bit-identical on a half-iteration?
     python tools/lib_equal.py libA libB [f] [solver] [scale] [gram mode] [presplit]
-Each library runs in its own process (CUMF_ALS_LIB, other CUMF_ALS_* switches inherited); the factors after two iterations on
-the Netflix shape (scaled by `scale`) and the fused train-SSE bins of one more Theta update ("-" where the plans cannot
-deliver them) are compared bit for bit, and so is the name of the last Gram kernel.  Also printed: the plans' chunked rows
-(cumf_plan_info [2]) and the rows of at most 32 ratings, X side / Theta side.  The SSE bins are sums of fp64 atomics: where several
-rows share a bin their bits can differ between two runs of ONE library (profiles/r07/route_equal_parent_self.txt)."""
+Each library runs in its own process (CUMF_ALS_LIB, other CUMF_ALS_* switches inherited), one after the other, for at most
+LIB_EQUAL_TIMEOUT seconds (300) each; libB is not started if libA's process failed, died on a signal or ran out of time.  The
+factors after two iterations on the Netflix shape (scaled by `scale`) and the fused train-SSE bins of one more Theta update ("-"
+where the plans cannot deliver them) are compared bit for bit, and so is the name of the last Gram kernel.  Also printed: the
+plans' chunked rows (cumf_plan_info [2]) and the rows of at most 32 ratings, X side / Theta side.  The SSE bins are sums of fp64
+atomics: where several rows share a bin their bits can differ between two runs of ONE library
+(profiles/r07/route_equal_parent_self.txt).  Exit status: 0 BIT-IDENTICAL, 1 DIFFERENT, 2 a process failed."""
 import hashlib, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
@@ -33,17 +35,17 @@ facts = "chunked {}/{} short {}/{}".format(sum(p.n_multi_rows for p in eng.x_pla
                                           short(r.csr_indptr.cpu().numpy()), short(r.csc_indptr.cpu().numpy()))
 print(h(eng.XT), h(eng.thetaT), sse, name, facts)
 ''' % ROOT
-a, b = sys.argv[1], sys.argv[2]
-f = sys.argv[3] if len(sys.argv) > 3 else "100"
-solver = sys.argv[4] if len(sys.argv) > 4 else "lu"
-scale = sys.argv[5] if len(sys.argv) > 5 else "0.3"
-gram = sys.argv[6] if len(sys.argv) > 6 else "auto"
-presplit = sys.argv[7] if len(sys.argv) > 7 else "auto"
+a, b, f, solver, scale, gram, presplit = (sys.argv[1:] + ["100", "lu", "0.3", "auto", "auto"][len(sys.argv) - 3:])[:7]
 outs = []
 for lib in (a, b):
     env = dict(os.environ, CUMF_ALS_LIB=os.path.join(ROOT, lib))
-    o = subprocess.run([sys.executable, "-c", CHILD, f, solver, scale, gram, presplit], env=env, capture_output=True, text=True)
-    line = [l for l in o.stdout.splitlines() if l.strip()][-1] if o.stdout.strip() else o.stderr[-400:]
-    outs.append(line)
-    print(lib, line)
+    try:
+        o = subprocess.run([sys.executable, "-c", CHILD, f, solver, scale, gram, presplit], env=env, capture_output=True, text=True,
+                           timeout=float(os.environ.get("LIB_EQUAL_TIMEOUT", "300")), check=True)
+        outs.append(o.stdout.strip().splitlines()[-1])
+    except (subprocess.SubprocessError, IndexError) as e:  # non-zero status, a signal, the time limit, no output
+        print(f"{lib}: {type(e).__name__} {getattr(e, 'returncode', '')}; stopping", str(getattr(e, "stderr", ""))[-400:], file=sys.stderr)
+        sys.exit(2)
+    print(lib, outs[-1])
 print("BIT-IDENTICAL" if outs[0].split()[:4] == outs[1].split()[:4] else "DIFFERENT")
+sys.exit(outs[0].split()[:4] != outs[1].split()[:4])
