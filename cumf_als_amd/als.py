@@ -18,6 +18,9 @@
 * `heldout_ranks`, `rank_metrics` (include/cumf_rank_capi.h): the rank of every held-out entry among all eligible
   candidates, by the same fused scoring, and AUC / MPR / MRR / MAP / precision, recall and NDCG at any cut-off from those
   ranks; both engines expose them as `heldout_ranks(side)` and `full_ranking_metrics(side, ks)`.
+* `update_biased`, `predict_biased`, `sse_biased`, `bias_mean` (include/cumf_bias_capi.h): explicit ALS with a global mean
+  and user and item biases, r^ = mu + b_u + c_i + x_u . theta_i, each half-iteration the fused update at f + 2 on augmented
+  tables and residual ratings; `BiasedALSEngine` trains it, and ranks and evaluates by the biased prediction.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -969,3 +972,202 @@ class ImplicitALSEngine(_Engine):
         """The implicit objective of the current factors (fp64)."""
         return float(implicit_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.XT, self.thetaT, self.lam,
                                    self.alpha, self.reg).item())
+
+
+# ---------------------------------------------------------------------------------------
+# biased explicit ALS (include/cumf_bias_capi.h)
+# ---------------------------------------------------------------------------------------
+
+BIAS_SIDE_X, BIAS_SIDE_THETA = 0, 1
+
+
+def _bias_side(side) -> int:
+    if side in (BIAS_SIDE_X, "x"):
+        return BIAS_SIDE_X
+    if side in (BIAS_SIDE_THETA, "theta"):
+        return BIAS_SIDE_THETA
+    raise ValueError(f"side must be 'x' or 'theta', got {side!r}")
+
+
+def bias_available(f: int, solver="cg") -> bool:
+    """cumf_bias_available: even f >= 2 with a fused route at f + 2 (f <= 204 in the default gram mode)."""
+    return bool(_libmod.load().cumf_bias_available(int(f), _solver_id(solver)))
+
+
+def update_biased(plan: Plan, colidx, val, gather, gather_bias, update, own_bias, side, mu: float, lambda_: float,
+                  lambda_bias: float, solver="cg", cg_iters: int = 6, bins=None):
+    """One biased half-iteration over the plan's rows (cumf_bias_update): `plan` made at F = f + 2, `gather` and `update`
+    the augmented serving tables (rows x F), `gather_bias` and `own_bias` their bias vectors, side "x" (own bias in column
+    f) or "theta" (column f + 1).  With `bins` (an fp64 tensor [SSE_BINS], ADDED to) the train SSE of the plan's rows comes
+    with it, where `fused_sse_available(plan, solver)`."""
+    import torch
+
+    lib = _libmod.load()
+    _libmod.check(lib.cumf_check_gather_table(gather.shape[0], plan.f, _solver_id(solver), 0), "cumf_check_gather_table")
+    _libmod.check(lib.cumf_plan_set_gather_rows(plan._h, int(gather.shape[0])), "cumf_plan_set_gather_rows")
+    _libmod.check(lib.cumf_bias_update(plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32),
+                                       _dp(gather, torch.float32), _dp(gather_bias, torch.float32),
+                                       _dp(update, torch.float32), _dp(own_bias, torch.float32), plan.f - 2,
+                                       _bias_side(side), float(mu), float(lambda_), float(lambda_bias), _solver_id(solver),
+                                       int(cg_iters), _dp(bins, torch.float64), _stream()), "cumf_bias_update")
+    return update
+
+
+def residual_biased(val, colidx, bias, mu: float, out=None):
+    """(val - mu) - bias[colidx] in fp32, two roundings (cumf_bias_residual): the ratings a biased half-iteration solves."""
+    import torch
+
+    if out is None:
+        out = torch.empty_like(val)
+    _libmod.check(_libmod.load().cumf_bias_residual(_dp(val, torch.float32), _dp(colidx, torch.int32), int(val.numel()),
+                                                    _dp(bias, torch.float32), float(mu), _dp(out, torch.float32), _stream()),
+                  "cumf_bias_residual")
+    return out
+
+
+def predict_biased(rows, cols, XA, TA, mu: float, clip=None, out=None):
+    """mu + the fp32 fmaf chain of XA[rows[e]] and TA[cols[e]] (cumf_bias_predict), clamped to clip = (lo, hi) when given;
+    rows and cols int32 on the device."""
+    import torch
+
+    count = int(rows.numel())
+    if out is None:
+        out = torch.empty(count, dtype=torch.float32, device=XA.device)
+    lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
+    _libmod.check(_libmod.load().cumf_bias_predict(
+        _dp(rows, torch.int32), _dp(cols, torch.int32), count, _dp(XA, torch.float32), _dp(TA, torch.float32),
+        int(XA.shape[1]), float(mu), lo, hi, _dp(out, torch.float32), _stream()), "cumf_bias_predict")
+    return out
+
+
+def sse_biased(val, row, col, XA, TA, mu: float, count: int | None = None, out=None):
+    """Sum of squared errors of the biased prediction over the first `count` ratings -> 1-element fp64 tensor
+    (cumf_bias_sse); bit-identical from run to run."""
+    import torch
+
+    if count is None:
+        count = val.numel()
+    if out is None:
+        out = torch.zeros(1, dtype=torch.float64, device=val.device)
+    _libmod.check(_libmod.load().cumf_bias_sse(
+        _dp(val, torch.float32), _dp(row, torch.int32), _dp(col, torch.int32), int(count), _dp(XA, torch.float32),
+        _dp(TA, torch.float32), int(XA.shape[1]), float(mu), _dp(out, torch.float64), _stream()), "cumf_bias_sse")
+    return out
+
+
+def bias_mean(val, count: int | None = None, out=None):
+    """The fp64 mean of the first `count` values -> 1-element fp64 tensor (cumf_bias_mean), summed in a fixed order."""
+    import torch
+
+    if count is None:
+        count = val.numel()
+    if out is None:
+        out = torch.zeros(1, dtype=torch.float64, device=val.device)
+    _libmod.check(_libmod.load().cumf_bias_mean(_dp(val, torch.float32), int(count), _dp(out, torch.float64), _stream()),
+                  "cumf_bias_mean")
+    return out
+
+
+class BiasedALSEngine(_Engine):
+    """Explicit-feedback ALS with a global mean and user / item biases on one GPU: r^ = mu + b_u + c_i + x_u . theta_i,
+    lambda n_u on the factors and lambda_bias n_u on the biases (lambda_bias defaults to lambda, mu to the training mean).
+    `XT` (m x F) and `thetaT` (n x F), F = f + 2, are the augmented serving tables [x | b | 1] and [theta | 1 | c]: their
+    plain dot product is r^ - mu, so the inherited recommend / ranking_metrics / heldout_ranks / full_ranking_metrics rank
+    by the biased prediction.  `user_bias`, `item_bias` and `mu` hold the rest of the model; `factors()` the f columns."""
+
+    def __init__(self, r, f: int, lambda_: float, lambda_bias: float | None = None, mu: float | None = None, solver="cg",
+                 cg_iters: int = 6, x_batch: int = 1, theta_batch: int = 1, chunk: int = 0):
+        import torch
+
+        if not bias_available(f, solver):
+            raise ValueError(f"biased ALS takes even f >= 2 with a fused half-iteration at f + 2 (f <= 204 in the default "
+                             f"gram mode); got f = {f}, {solver!r}")
+        self.lam = float(lambda_)
+        self.lam_bias = self.lam if lambda_bias is None else float(lambda_bias)
+        if not (self.lam > 0 and self.lam_bias > 0):
+            raise ValueError("biased ALS needs lambda > 0 and lambda_bias > 0")
+        self.solver, self.cg_iters = solver, int(cg_iters)
+        super().__init__(r, f + 2, x_batch, theta_batch, chunk)  # the plans and the tables at F
+        self.f, self.F = f, f + 2
+        for plans, gather_rows in ((self.x_plans, r.n), (self.t_plans, r.m)):
+            for p in plans:
+                _libmod.check(_libmod.load().cumf_plan_set_gather_rows(p._h, int(gather_rows)), "cumf_plan_set_gather_rows")
+        self.user_bias = torch.zeros(r.m, dtype=torch.float32, device=self.device)
+        self.item_bias = torch.zeros(r.n, dtype=torch.float32, device=self.device)
+        self.XT[:, f + 1] = 1.0
+        self.thetaT[:, f] = 1.0
+        if mu is None:
+            mu = float(np.float32(bias_mean(r.csr_data, r.nnz).item()))
+        self.mu = float(np.float32(mu))
+
+    def factors(self):
+        """(thetaT n x f, XT m x f): the factor columns of the augmented tables, as views."""
+        return self.thetaT[:, :self.f], self.XT[:, :self.f]
+
+    def init_factors(self, thetaT=None, XT=None, user_bias=None, item_bias=None, seed: int = 0):
+        """thetaT n x f and XT m x f factor arrays; the default theta is the plain engine's, X and both biases 0."""
+        import torch
+
+        f = self.f
+        if thetaT is None:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(seed)
+            thetaT = 0.2 * torch.rand((self.n, f), generator=g, dtype=torch.float32)
+        self.thetaT[:, :f] = torch.as_tensor(thetaT).reshape(self.n, f).to(self.device)
+        self.XT[:, :f] = 0.0 if XT is None else torch.as_tensor(XT).reshape(self.m, f).to(self.device)
+        for own, given, rows in ((self.user_bias, user_bias, self.m), (self.item_bias, item_bias, self.n)):
+            if given is None:
+                own.zero_()
+            else:
+                own.copy_(torch.as_tensor(given).reshape(rows))
+        self.XT[:, f], self.XT[:, f + 1] = self.user_bias, 1.0
+        self.thetaT[:, f], self.thetaT[:, f + 1] = 1.0, self.item_bias
+
+    def _half_x(self, bins=None):
+        for p in self.x_plans:
+            update_biased(p, self.r.csr_indices, self.r.csr_data, self.thetaT, self.item_bias, self.XT, self.user_bias,
+                          BIAS_SIDE_X, self.mu, self.lam, self.lam_bias, self.solver, self.cg_iters, bins)
+
+    def _half_theta(self, bins=None):
+        for p in self.t_plans:
+            update_biased(p, self.r.csc_indices, self.r.csc_data, self.XT, self.user_bias, self.thetaT, self.item_bias,
+                          BIAS_SIDE_THETA, self.mu, self.lam, self.lam_bias, self.solver, self.cg_iters, bins)
+
+    def update_x(self):
+        """update X and the user biases from thetaT and the item biases over the CSR rows."""
+        self._half_x()
+
+    def update_theta(self):
+        """update Theta and the item biases from XT and the user biases over the CSC columns."""
+        self._half_theta()
+
+    def update_theta_with_train_sse(self):
+        """update_theta AND the train SSE of the new model (fp64 scalar tensor) from the same kernels; None -- after a plain
+        update -- when the plans cannot deliver it (as ALSEngine.update_theta_with_train_sse)."""
+        import torch
+
+        if not all(fused_sse_available(p, self.solver) for p in self.t_plans):
+            self.update_theta()
+            return None
+        bins = torch.zeros(SSE_BINS, dtype=torch.float64, device=self.device)
+        self._half_theta(bins)
+        return bins.sum()
+
+    def train_sse(self):
+        """The train SSE of the current model (fp64 scalar tensor, cumf_bias_sse)."""
+        r = self.r
+        return sse_biased(r.csr_data, r.coo_row, r.csr_indices, self.XT, self.thetaT, self.mu, r.nnz)[0]
+
+    def rmse(self):
+        """(train, test) RMSE of the biased prediction, unclipped."""
+        r = self.r
+        te = sse_biased(r.test_data, r.test_row, r.test_col, self.XT, self.thetaT, self.mu, r.nnz_test)
+        return (float(self.train_sse().item() / max(r.nnz, 1)) ** 0.5, float(te.item() / max(r.nnz_test, 1)) ** 0.5)
+
+    def predict(self, rows, cols, clip=None):
+        """The predicted ratings of the pairs (rows[e], cols[e]) as an fp32 tensor on the device; clip = (lo, hi) clamps."""
+        import torch
+
+        rows = torch.as_tensor(rows).to(device=self.device, dtype=torch.int32).contiguous()
+        cols = torch.as_tensor(cols).to(device=self.device, dtype=torch.int32).contiguous()
+        return predict_biased(rows, cols, self.XT, self.thetaT, self.mu, clip)

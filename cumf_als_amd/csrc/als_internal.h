@@ -1,6 +1,7 @@
 // als_internal.h -- the core declarations shared by the HIP kernels and the host side of libALS.so: constants, kernel
-// arguments, routes, launchers, the plan and the scratch pool.  Implicit feedback, top-k, full ranking and NNLS each have a
-// header of their own (als_implicit.h, als_topk.h, als_rank.h, als_nnls.h) that only their own files include.
+// arguments, routes, launchers, the plan and the scratch pool.  Implicit feedback, top-k, full ranking, NNLS and biased ALS
+// each have a header of their own (als_implicit.h, als_topk.h, als_rank.h, als_nnls.h, als_bias.h) that only their own files
+// include.
 #ifndef CUMF_ALS_INTERNAL_H_
 #define CUMF_ALS_INTERNAL_H_
 
@@ -308,6 +309,9 @@ enum {
   kScratchRankMetrics = 17,
   // cumf_lu_solve_batched above f = 200: the batch the elimination in global memory factors in place of the caller's A
   kScratchLuWork = 18,
+  // biased ALS (als_bias.cpp): the residual ratings of a half-iteration, fp64 partial sums of the SSE and the mean
+  kScratchBiasResid = 19,
+  kScratchBiasPart = 20,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 // `count` elements of T (at least one) from the pool
@@ -340,6 +344,7 @@ struct cumf_plan {
   long rows = 0, row_begin = 0, row_end = 0;
   int f = 0, nb = 0, chunk = 0;
   long long plan_nnz = 0;  // ratings of the planned rows
+  long long entry_begin = 0;  // ... the first of them: entries [entry_begin, entry_begin + plan_nnz) of colidx / val
   long long chunk_nnz = 0;  // ... of which in chunked rows
   long n_items = 0, n_slots = 0, n_mrows = 0;
   long n_short = 0;  // whole rows of at most kShortRow ratings: the last n_short items (and the last of the w list)

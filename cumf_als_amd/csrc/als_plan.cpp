@@ -148,6 +148,7 @@ extern "C" int cumf_plan_create(cumf_plan_t** out, const void* rowptr_host, int 
   p->nb = nb_for_f(f);
   p->chunk = chunk;
   p->plan_nnz = rp(row_end) - rp(row_begin);
+  p->entry_begin = rp(row_begin);
   p->n_items = (long)n_it;
   p->n_short = n_short;
   p->n_slots = n_slots;

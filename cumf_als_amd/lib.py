@@ -1,5 +1,5 @@
 """ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h, cumf_dist_capi.h,
-cumf_implicit_capi.h, cumf_topk_capi.h, cumf_nnls_capi.h and cumf_rank_capi.h).
+cumf_implicit_capi.h, cumf_topk_capi.h, cumf_nnls_capi.h, cumf_rank_capi.h and cumf_bias_capi.h).
 
 The library is the product: there is no Python or CPU fallback.  `load()` raises
 when the shared object is missing or lacks a declared symbol.
@@ -113,10 +113,21 @@ RANK_ABI = {
     "cumf_heldout_ranks": (_i, [_fp, _l, _fp, _l, _i, _vp, _i, _ip, _vp, _i, _ip, _l, _ip, _ip, _vp]),
     "cumf_rank_metrics": (_i, [_ip, _ip, _l, _vp, _i, _fp, _l, C.POINTER(_i), _i, _vp, _vp]),
 }
+# include/cumf_bias_capi.h (biased explicit ALS, als_bias.cpp)
+BIAS_ABI = {
+    "cumf_bias_available": (_i, [_i, _i]),
+    "cumf_bias_update": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _f, _f, _i, _i, _vp, _vp]),
+    "cumf_bias_residual": (_i, [_fp, _ip, _l, _fp, _f, _fp, _vp]),
+    "cumf_bias_predict": (_i, [_ip, _ip, _l, _fp, _fp, _i, _f, _f, _f, _fp, _vp]),
+    "cumf_bias_sse": (_i, [_fp, _ip, _ip, _l, _fp, _fp, _i, _f, _vp, _vp]),
+    "cumf_bias_mean": (_i, [_fp, _l, _vp, _vp]),
+}
 ABI_BY_HEADER = {"cumf_als_capi.h": C_ABI, "cumf_dist_capi.h": DIST_ABI, "cumf_implicit_capi.h": IMPLICIT_ABI,
-                 "cumf_topk_capi.h": TOPK_ABI, "cumf_nnls_capi.h": NNLS_ABI, "cumf_rank_capi.h": RANK_ABI}
+                 "cumf_topk_capi.h": TOPK_ABI, "cumf_nnls_capi.h": NNLS_ABI, "cumf_rank_capi.h": RANK_ABI,
+                 "cumf_bias_capi.h": BIAS_ABI}
 C_SYMBOLS, DIST_SYMBOLS, IMPLICIT_SYMBOLS = list(C_ABI), list(DIST_ABI), list(IMPLICIT_ABI)
 TOPK_SYMBOLS, NNLS_SYMBOLS, RANK_SYMBOLS = list(TOPK_ABI), list(NNLS_ABI), list(RANK_ABI)
+BIAS_SYMBOLS = list(BIAS_ABI)
 # C++-linkage drop-in symbols (include/als.h, include/cg.h) under the reference's mangled names
 CXX_SYMBOLS = [
     "_Z5doALSPKiS0_PKfS0_S0_S2_S0_PfS3_S0_S0_S2_iiillfiiii",
