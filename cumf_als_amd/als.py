@@ -9,7 +9,8 @@
   bench.py times and what the multi-GPU driver (`cumf_als_amd.dist`) builds on.
 * `ImplicitALSEngine` does the same for implicit feedback (include/cumf_implicit_capi.h): the
   confidence-weighted model of Hu, Koren and Volinsky, over `implicit_gram`, `update_implicit`,
-  `implicit_loss`.
+  `implicit_loss`.  `get_hermitian_implicit_partial` and `implicit_finish` are the two halves of a system that several
+  GPUs form together (`cumf_als_amd.dist_implicit`).
 * `nnls_solve`, `update_nonneg`, `update_implicit_nonneg` (include/cumf_nnls_capi.h): non-negative least squares on
   materialised systems by block principal pivoting; both engines take `nonnegative=True` to keep every factor >= 0.
 * `topk`, `ranking_metrics` (include/cumf_topk_capi.h): the k best candidates per query, scored by a fused HIP kernel
@@ -897,6 +898,48 @@ def get_hermitian_implicit(plan: Plan, colidx, val, gather, G, lambda_: float, a
         _dp(tt, torch.float32), _dp(rhs, torch.float32), f, float(lambda_), float(alpha), _reg_id(reg), _stream()),
         "cumf_get_hermitian_implicit")
     return tt, rhs
+
+
+def get_hermitian_implicit_partial(plan: Plan, colidx, val, gather, lambda_: float, alpha: float, reg="weighted",
+                                   packed=None, rhs=None):
+    """The PARTIAL implicit systems of the plan's rows over the entries of this plan alone, as packed upper triangles
+    packed[rows, f(f+1)/2] = sum w y y^T (+ lambda n_local on the diagonal when reg is "weighted") and rhs[rows,f] =
+    sum_{r>0} (1+w) y (cumf_get_hermitian_implicit_partial): G is not added, so the partials of row slabs sum to the
+    full system minus G -- the multi-GPU reduction payload, completed by `implicit_finish`."""
+    import torch
+
+    f, rows = plan.f, plan.batch_rows
+    if packed is None:
+        packed = torch.empty((rows, f * (f + 1) // 2), dtype=torch.float32, device=gather.device)
+    if rhs is None:
+        rhs = torch.empty((rows, f), dtype=torch.float32, device=gather.device)
+    if tuple(packed.shape) != (rows, f * (f + 1) // 2) or tuple(rhs.shape) != (rows, f):
+        raise ValueError(f"get_hermitian_implicit_partial: packed must be [{rows}, {f * (f + 1) // 2}] and rhs "
+                         f"[{rows}, {f}] (got {tuple(packed.shape)}, {tuple(rhs.shape)})")
+    _libmod.check(_libmod.load().cumf_get_hermitian_implicit_partial(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(gather, torch.float32),
+        _dp(packed, torch.float32), _dp(rhs, torch.float32), f, float(lambda_), float(alpha), _reg_id(reg), _stream()),
+        "cumf_get_hermitian_implicit_partial")
+    return packed, rhs
+
+
+def implicit_finish(packed, G, reg_add: float, tt=None):
+    """tt[batch,f,f] = packed (upper triangles, mirrored) + G, then + reg_add on the diagonal (cumf_implicit_finish):
+    the summed partials of `get_hermitian_implicit_partial` become solvable systems.  reg_add: lambda when reg is
+    "plain", 0 when it is "weighted" (the partials carry lambda n already)."""
+    import torch
+
+    f = int(G.shape[-1])
+    batch = int(packed.shape[0])
+    if tuple(G.shape) != (f, f) or packed.shape[1] != f * (f + 1) // 2 or (tt is not None and tuple(tt.shape) != (batch, f, f)):
+        raise ValueError(f"implicit_finish: packed [batch, f(f+1)/2], G [f, f] and tt [batch, f, f] do not agree "
+                         f"({tuple(packed.shape)}, {tuple(G.shape)}, {None if tt is None else tuple(tt.shape)})")
+    if tt is None:
+        tt = torch.empty((batch, f, f), dtype=torch.float32, device=packed.device)
+    _libmod.check(_libmod.load().cumf_implicit_finish(_dp(packed, torch.float32), _dp(G, torch.float32), float(reg_add),
+                                                      _dp(tt, torch.float32), batch, f, _stream()),
+                  "cumf_implicit_finish")
+    return tt
 
 
 def update_implicit(plan: Plan, colidx, val, gather, G, update, lambda_: float, alpha: float, reg="weighted", solver="cg",

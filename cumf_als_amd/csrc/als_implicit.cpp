@@ -294,6 +294,37 @@ extern "C" int cumf_get_hermitian_implicit(const cumf_plan_t* p, const int* coli
   return 0;
 }
 
+extern "C" int cumf_get_hermitian_implicit_partial(const cumf_plan_t* p, const int* colidx, const float* val,
+                                                   const float* gather, float* packed, float* rhs, int f, float lambda,
+                                                   float alpha, int reg_mode, void* stream) {
+  int rc = check_args("cumf_get_hermitian_implicit_partial", p, f, reg_mode);
+  if (rc) return rc;
+  if (!packed || !rhs) {
+    fprintf(stderr, "cumf_get_hermitian_implicit_partial: packed and rhs must not be NULL\n");
+    return (int)hipErrorInvalidValue;
+  }
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchLease lease;
+  // the plan lists EVERY row of its batch as an item (a row without entries as one item of length 0), so the item pass itself
+  // writes the all-zero partials of the rows that have no entry in this plan: no clearing pass over the batch
+  ImplicitArgs a = base_implicit_args(p, colidx, val, gather, nullptr, f, lambda, alpha, reg_mode);
+  a.tt = packed;
+  a.rhs = rhs;
+  if ((rc = scratch(s, kScratchImpSlots, (size_t)p->n_slots * ((size_t)f * f + f), &a.slots))) return rc;
+  CUMF_HIP_CHECK(launch_implicit_partial(a, p->n_items, p->n_mrows, s));
+  return 0;
+}
+
+extern "C" int cumf_implicit_finish(const float* packed, const float* G, float reg_add, float* tt, long batch, int f,
+                                    void* stream) {
+  if (!implicit_f_ok(f) || batch < 0 || !G || (batch > 0 && (!packed || !tt))) {
+    fprintf(stderr, "cumf_implicit_finish: needs even 8 <= f <= 128 (got %d), batch >= 0 and non-NULL buffers\n", f);
+    return (int)hipErrorInvalidValue;
+  }
+  CUMF_HIP_CHECK(launch_implicit_finish(packed, G, reg_add, tt, batch, f, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
 extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx, const float* val, const float* gather,
                                         const float* G, float* update, int f, float lambda, float alpha, int reg_mode,
                                         int solver, int cg_iters, void* stream) {

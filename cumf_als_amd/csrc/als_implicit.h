@@ -1,4 +1,4 @@
-// als_implicit.h -- implicit feedback: what als_implicit.hip / als_implicit_free.hip (kernels) and als_implicit.cpp (host side;
+// als_implicit.h -- implicit feedback: what als_implicit.hip (compiled in two parts) / als_implicit_free.hip (kernels) and als_implicit.cpp (host side;
 // include/cumf_implicit_capi.h) share.  als_nnls.cpp takes it too, for the empty-row helpers.
 #ifndef CUMF_ALS_IMPLICIT_H_
 #define CUMF_ALS_IMPLICIT_H_
@@ -29,8 +29,8 @@ struct ImplicitArgs {
   const int* colidx;
   const float* val;
   const float* gather;
-  const float* G;  // f x f Gram of `gather`
-  float* tt;       // systems, f x f each
+  const float* G;  // f x f Gram of `gather` (not read by the packed output mode)
+  float* tt;       // systems, f x f each (packed output mode: upper triangles, f (f + 1) / 2 each)
   float* rhs;      // right-hand sides (may be null)
   float* slots;    // per-chunk partials, f x f + f each
   float* update;   // short-row CG: warm start in, solution out
@@ -44,6 +44,12 @@ size_t implicit_gram_part_floats(long rows, int f);
 hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, float* G, double* G64, hipStream_t stream);
 // systems of items [0, n_items) of a's lists, then the n_mrows chunked rows
 hipError_t launch_implicit_hermitian(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream);
+// the same pass in the packed output mode: the partial systems of cumf_get_hermitian_implicit_partial -- a.tt is a batch of
+// packed upper triangles (f (f + 1) / 2 floats each), a.G is not read
+hipError_t launch_implicit_partial(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream);
+// tt[b] = packed[b] (mirrored) + G, then + reg_add on the diagonal (cumf_implicit_finish)
+hipError_t launch_implicit_finish(const float* packed, const float* G, float reg_add, float* tt, long batch, int f,
+                                  hipStream_t stream);
 // Gram-free CG of the whole rows of items [first, first + count) (at most kShortRow entries each)
 hipError_t launch_implicit_short_cg(const ImplicitArgs& a, long first, long count, hipStream_t stream);
 hipError_t launch_implicit_copy_rows(const int* rows, long count, int f, const float* in, float* out, bool scatter,

@@ -2,7 +2,7 @@
 //
 // A stored entry (u, i, r) has the weight w = alpha |r| and the preference p = (r > 0).  One side's systems are
 //   A_u = G + sum_i w_ui y_i y_i^T + reg_u I,   b_u = sum_{r > 0} (1 + w_ui) y_i,   G = Y^T Y over the whole table.
-// Four pieces, all on exact fp32 arithmetic with fixed reduction orders (bit-identical from run to run, no float atomics):
+// Five pieces, all on exact fp32 arithmetic with fixed reduction orders (bit-identical from run to run, no float atomics):
 //   implicit_gram_partial_kernel   G of a table: one workgroup per slab of kImpGramSlab rows accumulates the upper 16 x 16 tiles
 //                                  of its slab on v_mfma_f32_16x16x4_f32 and writes them; implicit_gram_reduce_kernel sums the
 //                                  slab partials in slab order in fp64 and writes both triangles (exactly symmetric);
@@ -10,13 +10,26 @@
 //                                  sum w y y^T on the same MFMA (the A operand scaled by w), b on the VALU; a whole row writes
 //                                  G + sum + reg I, a chunk its raw partial, which implicit_slot_reduce_kernel sums in chunk
 //                                  order (fp64) for the row -- the partial-slot scheme of the explicit path;
+//   ... in the packed output mode   the same item kernel with another epilogue (implicit_hermitian_kernel<kImpPacked + FT>):
+//                                  the PARTIAL system a rank contributes to a multi-GPU sum -- no G, packed upper triangle,
+//                                  lambda n on the diagonal in weighted mode; implicit_slot_reduce_packed_kernel likewise;
+//                                  implicit_finish_kernel adds G (and lambda in plain mode) to the summed partials;
 //   implicit_short_cg_kernel       rows of at most kShortRow entries: the CG of als_short.hip without forming A_u,
 //                                  A p = G p + T^T (w o (T p)) + reg p, G shared by the waves of a workgroup in LDS;
 //   implicit_loss_*                the objective from the stored entries and two fp64 Grams.
+//
+// Compiled twice (Makefile): as als_implicit_kernels.o, everything but the packed output mode, and with
+// -DCUMF_IMPLICIT_PART=1 as als_implicit_partial.o, the packed output mode alone -- the item kernel's second set of
+// instantiations, its slot reduce and the finish kernel.  An object of their own keeps the code generated for the first
+// set exactly what it was before the second existed (tools/kernels_equal.py).
 #include <hip/hip_runtime.h>
 
 #include "als_device.h"
 #include "als_implicit.h"
+
+#ifndef CUMF_IMPLICIT_PART
+#define CUMF_IMPLICIT_PART 0
+#endif
 
 namespace cumf {
 
@@ -83,6 +96,7 @@ __device__ __forceinline__ void implicit_stage_tiles(const float* ys, const floa
   }
 }
 
+#if CUMF_IMPLICIT_PART == 0
 // ---- 1. G = Y^T Y
 
 template <int FT>
@@ -130,10 +144,22 @@ __global__ __launch_bounds__(kImpThreads) void implicit_gram_reduce_kernel(const
   if (G64) G64[e] = s;
 }
 
+#endif  // CUMF_IMPLICIT_PART == 0
+
 // ---- 2. materialised systems
 
-template <int FT>
+// element (i, j), i <= j, of a packed upper triangle of order f (row-major: the layout of cumf_get_hermitian_packed)
+__host__ __device__ constexpr int implicit_packed_index(int i, int j, int f) { return i * f - i * (i - 1) / 2 + (j - i); }
+
+// MODE = FT: the systems of cumf_get_hermitian_implicit.  MODE = kImpPacked + FT, the packed output mode: the partial system
+// of cumf_get_hermitian_implicit_partial -- a.tt is the batch of packed upper triangles, G is not read, and the diagonal of a
+// whole row gets lambda n (weighted mode) or nothing (plain mode).  A chunk writes its raw partial either way.  (One template
+// argument, so that the instantiations of the first mode keep their symbols.)
+constexpr int kImpPacked = 16;
+template <int MODE>
 __global__ __launch_bounds__(kImpThreads) void implicit_hermitian_kernel(const ImplicitArgs a) {
+  constexpr bool PACKED = MODE >= kImpPacked;
+  constexpr int FT = MODE % kImpPacked;
   constexpr int FP = 16 * FT, P = implicit_stage_pitch(FP), TPW = ImplicitTiles<FT>::TPW, NT = ImplicitTiles<FT>::NT;
   __shared__ float ys[kImpStage * P];
   __shared__ float sw[kImpStage], sc[kImpStage];
@@ -173,9 +199,12 @@ __global__ __launch_bounds__(kImpThreads) void implicit_hermitian_kernel(const I
   float reg = 0.f;
   if (whole) {
     const long long dst = a.item_dst ? a.item_dst[item] : a.item_row[item] - a.row_begin;
-    out = a.tt + (size_t)dst * ff;
+    out = a.tt + (size_t)dst * (PACKED ? (size_t)f * (f + 1) / 2 : ff);
     rhs = a.rhs ? a.rhs + (size_t)dst * f : nullptr;
-    reg = a.reg_mode == kImpRegPlain ? a.lambda : a.lambda * (float)a.item_rowlen[item];
+    if constexpr (PACKED)
+      reg = a.reg_mode == kImpRegPlain ? 0.f : a.lambda * (float)a.item_rowlen[item];
+    else
+      reg = a.reg_mode == kImpRegPlain ? a.lambda : a.lambda * (float)a.item_rowlen[item];
   } else {  // raw partial of one chunk: f x f + f floats per slot
     out = a.slots + (size_t)slot * (ff + f);
     rhs = out + ff;
@@ -189,7 +218,13 @@ __global__ __launch_bounds__(kImpThreads) void implicit_hermitian_kernel(const I
         const int gi = 16 * T.I[q] + 4 * (lane >> 4) + r;
         if (gi < f && gj < f) {
           float v = acc[q][r];
-          if (whole) {
+          if constexpr (PACKED) {
+            if (whole) {  // the upper triangle only (a diagonal tile holds both halves)
+              if (gi == gj) v += reg;
+              if (gi <= gj) out[implicit_packed_index(gi, gj, f)] = v;
+              continue;
+            }
+          } else if (whole) {
             v = a.G[gi * f + gj] + v;
             if (gi == gj) v += reg;
           }
@@ -202,6 +237,7 @@ __global__ __launch_bounds__(kImpThreads) void implicit_hermitian_kernel(const I
   if (rhs && (int)threadIdx.x < f) rhs[threadIdx.x] = bacc;
 }
 
+#if CUMF_IMPLICIT_PART == 0
 // rows cut into chunks: G + (the chunk partials summed in chunk order, fp64) + reg I
 __global__ __launch_bounds__(kImpThreads) void implicit_slot_reduce_kernel(const ImplicitArgs a) {
   const int m = blockIdx.x, f = a.f;
@@ -221,6 +257,45 @@ __global__ __launch_bounds__(kImpThreads) void implicit_slot_reduce_kernel(const
   }
 }
 
+#else  // CUMF_IMPLICIT_PART == 1
+// the packed output mode of the slot reduce: the upper triangle of the chunk partials summed in chunk order (fp64), with
+// lambda n on the diagonal in weighted mode; G is not read
+__global__ __launch_bounds__(kImpThreads) void implicit_slot_reduce_packed_kernel(const ImplicitArgs a) {
+  const int m = blockIdx.x, f = a.f;
+  const int slot0 = a.mrow_slot0[m], ns = a.mrow_nslots[m];
+  const long long dst = a.mrow_dst ? a.mrow_dst[m] : a.mrow_row[m] - a.row_begin;
+  const double reg = a.reg_mode == kImpRegPlain ? 0.0 : (double)(a.lambda * (float)a.mrow_rowlen[m]);
+  const int ff = f * f;
+  for (int e = threadIdx.x; e < ff + f; e += kImpThreads) {
+    const int i = e / f, j = e - i * f;
+    if (e < ff && i > j) continue;  // below the diagonal
+    double s = 0.0;
+    for (int k = 0; k < ns; ++k) s += (double)a.slots[(size_t)(slot0 + k) * (ff + f) + e];
+    if (e < ff)
+      a.tt[(size_t)dst * (f * (f + 1) / 2) + implicit_packed_index(i, j, f)] = (float)(s + (i == j ? reg : 0.0));
+    else if (a.rhs)
+      a.rhs[(size_t)dst * f + (e - ff)] = (float)s;
+  }
+}
+
+// tt[b] = (the packed upper triangle b, mirrored) + G, then + reg_add on the diagonal: two fp32 additions in this order
+__global__ __launch_bounds__(kImpThreads) void implicit_finish_kernel(const float* __restrict__ packed,
+                                                                      const float* __restrict__ G, float reg_add,
+                                                                      float* __restrict__ tt, long long batch, int f) {
+  const int ff = f * f, pk = f * (f + 1) / 2;
+  const long long total = batch * ff;
+  for (long long e = (long long)blockIdx.x * kImpThreads + threadIdx.x; e < total; e += (long long)gridDim.x * kImpThreads) {
+    const long long b = e / ff;
+    const int r = (int)(e - b * ff), i = r / f, j = r - i * f;
+    float v = packed[(size_t)b * pk + (i < j ? implicit_packed_index(i, j, f) : implicit_packed_index(j, i, f))] + G[r];
+    if (i == j) v += reg_add;
+    tt[e] = v;
+  }
+}
+
+#endif  // CUMF_IMPLICIT_PART
+
+#if CUMF_IMPLICIT_PART == 0
 // ---- 3. Gram-free CG of short rows (the pattern of als_short.hip, with the weights and G)
 
 // the whole row with at most N entries in flight (N = 8, 16, 32 >= n); TWO: f > 64, the lanes hold two features each;
@@ -508,5 +583,30 @@ hipError_t launch_implicit_loss(const int* rowptr, const int* colidx, const floa
   return launch_kernel(implicit_loss_final_kernel, dim3(1), dim3(kImpThreads), 0, stream, (const double*)part,
                        (int)kImpLossBlocks, Gx, Gy, f, lambda, reg_mode, out);
 }
+
+#else  // CUMF_IMPLICIT_PART == 1
+
+hipError_t launch_implicit_partial(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream) {
+  if (n_items > 0) {
+    const hipError_t e = with_nb<1, 8>((a.f + 15) / 16, [&](auto ft) {
+      return launch_item_kernel(implicit_hermitian_kernel<kImpPacked + decltype(ft)::value>, dim3((unsigned)n_items),
+                                dim3(kImpThreads), 0, stream, a);
+    });
+    if (e != hipSuccess) return e;
+  }
+  if (n_mrows > 0)
+    return launch_kernel(implicit_slot_reduce_packed_kernel, dim3((unsigned)n_mrows), dim3(kImpThreads), 0, stream, a);
+  return hipSuccess;
+}
+
+hipError_t launch_implicit_finish(const float* packed, const float* G, float reg_add, float* tt, long batch, int f,
+                                  hipStream_t stream) {
+  if (batch <= 0) return hipSuccess;
+  const long long blocks = ((long long)batch * f * f + kImpThreads - 1) / kImpThreads;
+  return launch_kernel(implicit_finish_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kImpThreads), 0, stream,
+                       packed, G, reg_add, tt, (long long)batch, f);
+}
+
+#endif  // CUMF_IMPLICIT_PART
 
 }  // namespace cumf

@@ -91,6 +91,8 @@ IMPLICIT_ABI = {
     "cumf_implicit_available": (_i, [_i, _i]),
     "cumf_implicit_gram": (_i, [_fp, _l, _i, _fp, _vp]),
     "cumf_get_hermitian_implicit": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _fp, _i, _f, _f, _i, _vp]),
+    "cumf_get_hermitian_implicit_partial": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _i, _f, _f, _i, _vp]),
+    "cumf_implicit_finish": (_i, [_fp, _fp, _f, _fp, _l, _i, _vp]),
     "cumf_als_update_implicit": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _i, _f, _f, _i, _i, _i, _vp]),
     "cumf_implicit_loss": (_i, [_ip, _ip, _fp, _fp, _fp, _l, _l, _i, _f, _f, _i, _vp, _vp]),
 }

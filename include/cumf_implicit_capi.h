@@ -11,8 +11,10 @@
  *
  * Conventions of cumf_als_capi.h: DEVICE pointers of the calling process, `stream` a hipStream_t passed as void* (NULL =
  * the default stream), 0 on success or a HIP error code after printing file/line to stderr, no CPU fallback.  Plans are
- * the cumf_plan_t of cumf_als_capi.h.  Scope: one GPU; even f with 8 <= f <= 512 for CUMF_SOLVER_CG_MATFREE,
- * cumf_implicit_gram and cumf_implicit_loss, even f with 8 <= f <= 128 for everything else; anything else is refused.
+ * the cumf_plan_t of cumf_als_capi.h.  Scope: every entry point works on the calling process's GPU (several GPUs:
+ * cumf_get_hermitian_implicit_partial + cumf_implicit_finish around the caller's own reduction, as
+ * cumf_als_amd/dist_implicit.py does); even f with 8 <= f <= 512 for CUMF_SOLVER_CG_MATFREE, cumf_implicit_gram and
+ * cumf_implicit_loss, even f with 8 <= f <= 128 for everything else; anything else is refused.
  * Every result is bit-identical from run to run (fixed-order reductions, no float atomics).
  */
 #ifndef CUMF_IMPLICIT_CAPI_H_
@@ -44,6 +46,30 @@ int cumf_implicit_gram(const float* table, long rows, int f, float* G, void* str
 int cumf_get_hermitian_implicit(const cumf_plan_t* plan, const int* colidx, const float* val, const float* gather,
                                 const float* G, float* tt, float* rhs, int f, float lambda, float alpha, int reg_mode,
                                 void* stream);
+
+/* The PARTIAL systems of the plan's rows over the stored entries of THIS plan alone -- what one rank of a multi-GPU run
+ * contributes when the gather table is row-sharded (the plan over the slab-local CSC, `gather` the slab of the table):
+ *   packed[row - row_begin]  f (f + 1) / 2 floats, the upper triangle in row-major order (the layout of
+ *                            cumf_get_hermitian_packed): sum over the plan's entries of w y y^T, plus lambda n_local on the
+ *                            diagonal with CUMF_IMPLICIT_REG_WEIGHTED (n_local = the row's entries in this plan); nothing
+ *                            is added with CUMF_IMPLICIT_REG_PLAIN;
+ *   rhs[row - row_begin]     f floats: sum_{r > 0} (1 + w) y.
+ * G is not added and not read: the partials of the ranks sum to the full system minus G (and minus lambda I in plain
+ * mode), which cumf_implicit_finish completes.  A row without entries in this plan gets all-zero output, written by the
+ * kernel itself (a plan lists every row of its batch).  Rows cut into chunks are summed over per-chunk partials in chunk
+ * order in fp64, as in cumf_get_hermitian_implicit.  The same accumulation as cumf_get_hermitian_implicit: only the
+ * epilogue differs.  Even 8 <= f <= 128. */
+int cumf_get_hermitian_implicit_partial(const cumf_plan_t* plan, const int* colidx, const float* val, const float* gather,
+                                        float* packed, float* rhs, int f, float lambda, float alpha, int reg_mode,
+                                        void* stream);
+
+/* Summed partials -> solvable systems: for every b < batch and i, j < f, in this order of fp32 operations,
+ *   t        = packed[b][(min(i, j), max(i, j))] + G[i][j]      one fp32 addition
+ *   tt[b][i][j] = (i == j) ? t + reg_add : t                      a second fp32 addition on the diagonal
+ * tt: batch x f x f, both triangles; exactly symmetric when G is (cumf_implicit_gram's is; so is a sum of them).
+ * reg_add: lambda with CUMF_IMPLICIT_REG_PLAIN, 0 with CUMF_IMPLICIT_REG_WEIGHTED (whose partials carry lambda n already).
+ * Even 8 <= f <= 128. */
+int cumf_implicit_finish(const float* packed, const float* G, float reg_add, float* tt, long batch, int f, void* stream);
 
 /* One implicit half-iteration over the plan's rows; update (rows x f) is the CG warm start and receives the solution.
  *   CUMF_SOLVER_CG: rows of at most 32 stored entries run a CG that never forms A_u (A p = G p + T^T (w o T p) + reg p,
