@@ -443,6 +443,15 @@ def last_kernel_name() -> str:
     return buf.value.decode()
 
 
+def last_tile_batches():
+    """(batches, rows per batch) of the pooled tile buffer in the last half-iteration (cumf_last_tile_batches): the whole rows
+    of the two-wave route (LU from f = 144, materialise from f = 112) go through it in batches of at most `rows per batch`;
+    (0, 0) when the call did not use the buffer.  CUMF_ALS_TILE_BUFFER_GB sizes it."""
+    info = (C.c_long * 2)()
+    _libmod.check(_libmod.load().cumf_last_tile_batches(info), "cumf_last_tile_batches")
+    return int(info[0]), int(info[1])
+
+
 def set_kernel_timing(enable: bool) -> None:
     _libmod.check(_libmod.load().cumf_set_kernel_timing(int(bool(enable))), "cumf_set_kernel_timing")
 

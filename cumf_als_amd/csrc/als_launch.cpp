@@ -1,12 +1,13 @@
 // als_launch.cpp -- carries out a route (workgroup, one-wave or two-wave path): which per-NB entry points of the kernel files
 // (als_internal.h) run on which item lists, for the run-time feature-block count; the standalone batched solvers; and the
-// optional HIP-event timing of the launch sequences.
+// optional HIP-event timing of the launch sequences; the tile-batch probe (cumf_last_tile_batches).
 // Host only: every kernel is launched by the kernel files' own launchers.
 #include <atomic>
 #include <mutex>
 #include <vector>
 
 #include "als_internal.h"
+#include "cumf_als_capi.h"
 
 namespace cumf {
 
@@ -37,6 +38,10 @@ TimedLaunch* timing_begin() {
 
 // the Gram(+solve) kernel the last half-iteration dispatched (bench.py reads its name for roofline.kernel)
 std::atomic<const void*> g_last_item_kernel{nullptr};
+
+// batches of the pooled tile buffer the newest launch_half_iteration carried out (0: it did not go through the buffer) and
+// the rows of one batch (PlanLists::part2_rows): cumf_last_tile_batches
+std::atomic<long> g_tile_batches{0}, g_tile_batch_rows{0};
 }  // namespace
 
 void set_kernel_timing(bool on) {
@@ -145,6 +150,7 @@ static hipError_t two_wave_items(const KernelArgs& a0, int mode, const Route& r,
   }
   // large LU / materialise (cumf_get_hermitian): in batches of part2_rows dense slots
   for (long w0 = 0; w0 < L.n_witems; w0 += L.part2_rows) {
+    g_tile_batches.fetch_add(1, std::memory_order_relaxed);
     const long cnt = L.n_witems - w0 < L.part2_rows ? L.n_witems - w0 : L.part2_rows;
     KernelArgs a = whole_row_items(a0, L, w0);
     a.dense_slots = 1;
@@ -161,6 +167,8 @@ static hipError_t two_wave_items(const KernelArgs& a0, int mode, const Route& r,
 
 hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& L, hipStream_t stream) {
   const int nb = nb_for_f(a.f);
+  g_tile_batches.store(0, std::memory_order_relaxed);
+  g_tile_batch_rows.store(L.part2_rows, std::memory_order_relaxed);
   // item phase (event 0 -> 1), then the chunked rows' solver (1 -> 2); the two-wave path interleaves them (item phase only)
   TimedLaunch* t = timing_begin();
   if (t) {
@@ -200,3 +208,11 @@ hipError_t launch_solve_batched(const float* A, const float* b, float* x, long b
 }
 
 }  // namespace cumf
+
+// Plain host state, no HIP call: how the newest launch_half_iteration of this process used the pooled tile buffer.
+extern "C" int cumf_last_tile_batches(long info[2]) {
+  if (!info) return (int)hipErrorInvalidValue;
+  info[0] = cumf::g_tile_batches.load(std::memory_order_relaxed);
+  info[1] = cumf::g_tile_batch_rows.load(std::memory_order_relaxed);
+  return 0;
+}

@@ -265,25 +265,41 @@ extern "C" int cumf_plan_info(const cumf_plan_t* p, long info[4]) {
   return 0;
 }
 
+namespace {
+
+// Rows of the pooled tile buffer for `n_rows` whole rows of `tile_bytes` each: the one place that sizes it.
+//   CUMF_ALS_TILE_BUFFER_GB set (read at every call, like CUMF_ALS_LU_EXACT in switches()): that many GiB as given, down to the
+//   tiles of one row -- what an operator sets on a card that other work fills, and what makes the batch loop of
+//   two_wave_items reachable by a test (tests/test_two_wave_batches_gpu.py).
+//   Default: sized for 288 GB of HBM, up to 48 GiB but never more than half of what is free and never below 2 GiB -- the
+//   Netflix Theta side at f = 200 (480 189 rows x 93 KB = 44.7 GB) then runs as ONE Gram launch + ONE LU launch instead of
+//   21 pairs of 2 GiB batches, each with its own tail.
+long tile_buffer_rows(long n_rows, size_t tile_bytes, hipStream_t stream) {
+  size_t cap;
+  if (const char* e = getenv("CUMF_ALS_TILE_BUFFER_GB")) {
+    const double gb = std::min(atof(e), 1048576.0);  // not a number, zero or negative: one row
+    cap = gb > 0.0 ? (size_t)(gb * (double)(1ull << 30)) : 0;
+  } else {
+    cap = (size_t)48 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      const size_t mine = scratch_capacity(stream, kScratchTiles);  // our own buffer counts as available
+      cap = std::min(cap, (free_b + mine) / 2);
+    }
+    cap = std::max(cap, (size_t)2 << 30);
+  }
+  return (long)std::max<size_t>(1, std::min<size_t>((size_t)n_rows, cap / tile_bytes));
+}
+
+}  // namespace
+
 // Work lists of a plan for launch_half_iteration; need_tiles: the dense-slot tile buffer (Route::whole == kSolveTileBuffer).
 int cumf::plan_lists(const cumf_plan_t* p, PlanLists* out, hipStream_t stream, bool need_tiles) {
   const size_t tile_bytes = (size_t)p->nb * (p->nb + 1) / 2 * 256 * sizeof(float);
   float* part2 = nullptr;
   long rows = 0;
   if (need_tiles && p->n_witems > 0) {
-    // Sized for 288 GB of HBM: up to 48 GiB (CUMF_ALS_TILE_BUFFER_GB), never more than half of what is free -- the
-    // Netflix Theta side at f = 200 (480 189 rows x 93 KB = 44.7 GB) then runs as ONE Gram launch + ONE LU launch
-    // instead of 21 pairs of 2 GiB batches, each with its own tail.
-    static const double cap_gb = getenv("CUMF_ALS_TILE_BUFFER_GB") ? atof(getenv("CUMF_ALS_TILE_BUFFER_GB")) : 48.0;
-    size_t cap = (size_t)(cap_gb * (double)(1ull << 30));
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const size_t mine = scratch_capacity(stream, kScratchTiles);  // our own buffer counts as available
-      cap = std::min(cap, (free_b + mine) / 2);
-    }
-    if (cap < ((size_t)2 << 30)) cap = (size_t)2 << 30;
-    rows = (long)std::min<size_t>((size_t)p->n_witems, cap / tile_bytes);
-    if (rows < 1) rows = 1;
+    rows = tile_buffer_rows(p->n_witems, tile_bytes, stream);
     void* q = nullptr;
     const int rc = scratch_get(stream, kScratchTiles, (size_t)rows * tile_bytes, &q);
     if (rc) return rc;

@@ -61,6 +61,7 @@ C_ABI = {
     "cumf_last_kernel_ms": (_i, [C.POINTER(_f), C.POINTER(_f)]),
     "cumf_kernel_ms_since_reset": (_i, [C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "cumf_last_kernel_name": (_i, [C.c_char_p, _i]),
+    "cumf_last_tile_batches": (_i, [C.POINTER(_l)]),
     "cumf_last_error": (_i, []),
     "cumf_release_scratch": (_i, []),
     "cumf_rand_init": (None, [_fp, _l, _f, _l]),

@@ -255,6 +255,11 @@ int cumf_kernel_ms_since_reset(float* item_kernel_ms, float* reduce_kernel_ms, i
 /* Demangled name of the Gram(+solve) kernel the last half-iteration dispatched, as rocprofv3 prints it
  * (e.g. "cumf::als_wave_kernel<7, 1, 100, 0>"); buf receives a NUL-terminated string ("" before any launch). */
 int cumf_last_kernel_name(char* buf, int cap);
+/* How the newest half-iteration of this process (fused update or materialising pass) used the pooled tile buffer that
+ * CUMF_ALS_TILE_BUFFER_GB sizes: info[0] = the batches of whole rows it sent through the buffer, 0 when the call did not go
+ * through it (f < 112, CG, LU below f = 144, a plan without whole rows); info[1] = the rows of one batch.  Plain host
+ * state: no HIP call, (0, 0) before any launch. */
+int cumf_last_tile_batches(long info[2]);
 
 /* Error state of the entry points that return a value instead of a code: cumf_doALS_ex / cumf_doALS / doALS
  * return NaN and set it when the opt-in gram mode "fast" meets data outside its range (the reference's own

@@ -12,3 +12,17 @@ def test_fused_available_matches_golden_table(alslib, monkeypatch):
     for knob in ("CUMF_ALS_GRAM", "CUMF_ALS_NO_BATCHED"):
         monkeypatch.delenv(knob, raising=False)
     assert table(alslib) == json.load(open(GOLDEN))
+
+
+def test_tile_batch_probe_before_any_launch(alslib):
+    """cumf_last_tile_batches is plain host state: before any half-iteration of the process it returns 0 and reports no batch
+    and no buffer rows (no HIP call, no GPU needed); a null pointer is refused."""
+    import ctypes as C
+
+    info = (C.c_long * 2)(-1, -1)
+    assert alslib.cumf_last_tile_batches(info) == 0
+    assert (info[0], info[1]) == (0, 0)
+    assert alslib.cumf_last_tile_batches(None) != 0
+    from cumf_als_amd import als
+
+    assert als.last_tile_batches() == (0, 0)
