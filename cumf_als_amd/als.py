@@ -22,6 +22,8 @@
 * `update_biased`, `predict_biased`, `sse_biased`, `bias_mean` (include/cumf_bias_capi.h): explicit ALS with a global mean
   and user and item biases, r^ = mu + b_u + c_i + x_u . theta_i, each half-iteration the fused update at f + 2 on augmented
   tables and residual ratings; `BiasedALSEngine` trains it, and ranks and evaluates by the biased prediction.
+* `update_matfree`, `matfree_available` (include/cumf_free_capi.h): the explicit half-iteration at any even 8 <= f <= 512 by a
+  CG that never forms a row's system; `ALSEngine(solver="cg_matfree")` and `do_als(solver="cg_matfree")` train with it.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -69,6 +71,8 @@ def do_als(csrrow, csrcol, csrval, cscrow, csccol, cscval, coorow, coorowtest, c
     mode "fast" meets data outside its range (the C entry point returns NaN and sets cumf_last_error).
     """
     lib = _libmod.load()
+    if _is_matfree(solver) and not matfree_available(f):  # solver "cg_matfree": both half-iterations as update_matfree
+        raise ValueError(f"solver 'cg_matfree' takes even 8 <= f <= 512 (got f = {f})")
     if thetat_init is None:
         rng = np.random.RandomState(0)
         thetat = (0.2 * rng.random_sample((n, f))).astype(np.float32)
@@ -99,7 +103,8 @@ def do_als(csrrow, csrcol, csrval, cscrow, csccol, cscval, coorow, coorowtest, c
         lib.cumf_last_error()
         rmse = lib.cumf_doALS_ex(*args, int(m), int(n), int(f), int(nnz), int(nnz_test), float(lambda_),
                                  int(iters), int(xbatch), int(thetabatch), int(deviceid),
-                                 _solver_id(solver), int(cg_iters), int(bool(fused)), int(bool(exact_test_grid)),
+                                 SOLVER_CG_MATFREE if _is_matfree(solver) else _solver_id(solver), int(cg_iters),
+                                 int(bool(fused)), int(bool(exact_test_grid)),
                                  int(bool(surpass_nan)), int(bool(quiet)), _hostptr(log, np.float32))
         err = lib.cumf_last_error()
     finally:
@@ -189,6 +194,34 @@ def update_fused(plan: Plan, colidx, val, gather, update, lambda_: float, solver
                                             _dp(gather, torch.float32), _dp(update, torch.float32), plan.f,
                                             float(lambda_), _solver_id(solver), int(cg_iters), _stream()),
                   "cumf_als_update_fused")
+    return update
+
+
+def matfree_available(f: int) -> bool:
+    """cumf_matfree_available: the matrix-free explicit half-iteration takes even 8 <= f <= 512."""
+    return bool(_libmod.load().cumf_matfree_available(int(f)))
+
+
+def _is_matfree(solver) -> bool:
+    # the explicit routes' own name for it: `_solver_id` keeps refusing it, as the fused and materialising entry points do
+    return isinstance(solver, str) and solver == "cg_matfree"
+
+
+def update_matfree(plan: Plan, colidx, val, gather, update, lambda_: float, cg_iters: int = 6):
+    """One explicit half-iteration over the plan's rows that never forms a system (cumf_als_update_matfree): the CG of
+    `update_fused(..., "cg")` -- warm start from `update`, at most `cg_iters` steps, exit when r.r < 1e-4 -- on
+    A v = T^T (T v) + n lambda v evaluated from the stored entries; even 8 <= f <= 512.  Rows without entries get 0."""
+    import torch
+
+    if not matfree_available(plan.f):
+        raise ValueError(f"update_matfree takes even 8 <= f <= 512 (got f = {plan.f})")
+    if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
+        raise ValueError(f"update_matfree: gather and update must be [rows, {plan.f}], the plan's f "
+                         f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
+    _libmod.check(_libmod.load().cumf_als_update_matfree(plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32),
+                                                         _dp(gather, torch.float32), _dp(update, torch.float32),
+                                                         float(lambda_), int(cg_iters), _stream()),
+                  "cumf_als_update_matfree")
     return update
 
 
@@ -783,7 +816,9 @@ class _Engine(_Recommender):
 
 class ALSEngine(_Engine):
     """Explicit-feedback ALS on one GPU: the dataset of `_Engine` + the fused (or, above the tile kernels' range,
-    materialising) half-iterations.
+    materialising) half-iterations.  solver "cg_matfree" (even 8 <= f <= 512) runs every half-iteration as `update_matfree`,
+    the same CG without any row's system: the route for f > 207, where "cg" and "lu" materialise f^2 floats per row; `fused`
+    is unused there, `nonnegative=True` with it is refused, and `update_theta_with_train_sse` is the plain update.
     """
 
     def __init__(self, r, f: int, lambda_: float, solver="cg", cg_iters: int = 6, x_batch: int = 1,
@@ -794,11 +829,16 @@ class ALSEngine(_Engine):
         self.solver, self.cg_iters = solver, cg_iters
         # nonnegative: every half-iteration is update_nonneg (materialise + NNLS); solver, cg_iters and fused are unused
         self.nonnegative = bool(nonnegative)
+        self.matfree = _is_matfree(solver)
+        if self.matfree and self.nonnegative:
+            raise ValueError("solver 'cg_matfree' has no non-negative form (nonnegative=True runs update_nonneg, f <= 128)")
+        if self.matfree and not matfree_available(f):
+            raise ValueError(f"solver 'cg_matfree' takes even 8 <= f <= 512 (got f = {f})")
         if self.nonnegative:
             _check_nonneg_f(f)
             self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
         # above the tile kernels' range (f > 207) the reference's unfused data flow runs (cumf_get_hermitian + batched solver)
-        self.fused = (not self.nonnegative and bool(fused)
+        self.fused = (not self.nonnegative and not self.matfree and bool(fused)
                       and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver))))
         super().__init__(r, f, x_batch, theta_batch, chunk)
         self._tt = None
@@ -810,6 +850,8 @@ class ALSEngine(_Engine):
         for p in plans:
             if self.nonnegative:
                 update_nonneg(p, colidx, val, gather, update, self.lam, stats=self.nnls_stats)
+            elif self.matfree:
+                update_matfree(p, colidx, val, gather, update, self.lam, self.cg_iters)
             elif self.fused:
                 update_fused(p, colidx, val, gather, update, self.lam, self.solver, self.cg_iters)
             else:

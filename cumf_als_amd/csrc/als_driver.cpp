@@ -23,6 +23,8 @@
 #include "als.h"
 #include "als_internal.h"
 #include "cumf_als_capi.h"
+#include "cumf_free_capi.h"
+#include "cumf_implicit_capi.h"  // CUMF_SOLVER_CG_MATFREE
 
 namespace {
 
@@ -133,15 +135,24 @@ extern "C" float cumf_doALS_ex(const int* csrRowIndexHostPtr, const int* csrColI
   if (!quiet) printf("*******parameters: m: %d, n:  %d, f: %d, nnz: %ld \n", m, n, f, nnz);
   if (X_BATCH < 1) X_BATCH = 1;
   if (THETA_BATCH < 1) THETA_BATCH = 1;
-  if (!cumf_fused_available(f, solver)) fused = 0;
+  // solver 2: both half-iterations on the matrix-free CG (cumf_free_capi.h), which forms no system: neither the fused
+  // kernels nor the Gram batch of the unfused path
+  const bool matfree = solver == CUMF_SOLVER_CG_MATFREE;
+  if (matfree && !cumf_matfree_available(f)) {
+    fprintf(stderr, "doALS: the matrix-free CG needs even 8 <= f <= 512 (got %d)\n", f);
+    DRV_CHECK(hipErrorInvalidValue);
+  }
+  if (matfree || !cumf_fused_available(f, solver)) fused = 0;
   // fp16 storage of the Gram batch (als.cu:779-783, 893-895): the reference's data flow by construction
   // (Gram batch in device memory + updateXWithCGHost_tt_fp16); CG only, like the reference
   const int tt_fp16 = cumf_get_tt_fp16() && solver == CUMF_SOLVER_CG;
   if (tt_fp16) fused = 0;
 
   // both factor tables are gathered from (Theta by the X update, X by the Theta update)
-  DRV_CHECK(cumf_check_gather_table(n, f, solver, !fused));
-  DRV_CHECK(cumf_check_gather_table(m, f, solver, !fused));
+  if (!matfree) {  // (the matrix-free kernels address the table with 64 bits)
+    DRV_CHECK(cumf_check_gather_table(n, f, solver, !fused));
+    DRV_CHECK(cumf_check_gather_table(m, f, solver, !fused));
+  }
   if (!quiet) printf("*******start allocating memory on GPU...\n");
   // The uploads (2 GB at the Netflix shape) run on a stream of their own while the host builds the plans below
   // (sorting ~500 k work items per side); pinned callers (main.cpp:50-69) get true overlap, pageable ones (the TF op) the
@@ -186,7 +197,7 @@ extern "C" float cumf_doALS_ex(const int* csrRowIndexHostPtr, const int* csrColI
 
   // unfused path: Gram batch `tt` (als.cu:782,897) + RHS (ythetaT / yTXT, als.cu:746,864)
   float *tt = nullptr, *rhs = nullptr;
-  if (!fused) {
+  if (!fused && !matfree) {
     long maxb = 0;
     for (long s : sx.size) maxb = s > maxb ? s : maxb;
     for (long s : st.size) maxb = s > maxb ? s : maxb;
@@ -222,7 +233,10 @@ extern "C" float cumf_doALS_ex(const int* csrRowIndexHostPtr, const int* csrColI
 
   auto half_iteration = [&](Side& s, const float* gather, float* update, double* sse_bins) {
     for (int b = 0; b < s.nbatch; ++b) {
-      if (fused) {
+      if (matfree) {
+        if (!quiet) printf("\tCG solver with fp32.\n");
+        DRV_CHECK(cumf_als_update_matfree(s.plans[b], s.d_colidx, s.d_val, gather, update, lambda, cg_iters, nullptr));
+      } else if (fused) {
         if (solver == CUMF_SOLVER_CG && !quiet) printf("\tCG solver with fp32.\n");
         if (sse_bins)
           DRV_CHECK(cumf_als_update_fused_sse(s.plans[b], s.d_colidx, s.d_val, gather, update, f, lambda, solver,
@@ -334,7 +348,9 @@ extern "C" float cumf_doALS(const int* csrRowIndexHostPtr, const int* csrColInde
                             const int THETA_BATCH, const int DEVICEID) {
   // run-time versions of the compile-time switches of als.cu:25-33
   const char* s = getenv("CUMF_ALS_SOLVER");
-  const int solver = (s && (strcmp(s, "lu") == 0 || strcmp(s, "LU") == 0)) ? CUMF_SOLVER_LU : CUMF_SOLVER_CG;
+  const int solver = (s && (strcmp(s, "lu") == 0 || strcmp(s, "LU") == 0)) ? CUMF_SOLVER_LU
+                     : (s && strcmp(s, "cg_matfree") == 0)                  ? CUMF_SOLVER_CG_MATFREE
+                                                                            : CUMF_SOLVER_CG;
   const char* pth = getenv("CUMF_ALS_PATH");
   const int fused = !(pth && strcmp(pth, "unfused") == 0);
   return cumf_doALS_ex(csrRowIndexHostPtr, csrColIndexHostPtr, csrValHostPtr, cscRowIndexHostPtr,

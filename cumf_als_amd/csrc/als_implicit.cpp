@@ -18,6 +18,7 @@ namespace cumf {
 // The plan lists its whole rows of at most kShortRow entries as the LAST n_short items; the items before them -- every chunk
 // and every longer whole row -- are the "long" items whose systems the CG route materialises into a compact batch.
 struct ImplicitLists {
+  bool built = false;     // the long-row / empty-row lists below (implicit_lists); the segments further down are built apart
   long n_long_items = 0;  // items [0, n_long_items) of the plan's list
   long n_long = 0;        // their rows, in the order of first appearance (longest first)
   long n_empty = 0;       // rows without stored entries
@@ -26,7 +27,8 @@ struct ImplicitLists {
   int* d_item_dst = nullptr;   // n_long_items: item -> compact index of its row
   int* d_mrow_dst = nullptr;   // n_mrows: chunked row -> compact index
   int* d_empty_row = nullptr;  // n_empty
-  // the matrix-free CG's segments and per-row lists (ImplicitFreeArgs), built on its first use; rows: row - row_begin
+  // the segments and per-row lists of the matrix-free CGs (ImplicitFreeArgs, FreeArgs of als_free.h), built on first use
+  // (plan_free_lists); rows: row - row_begin
   bool free_built = false;
   long n_seg = 0;
   char* d_free = nullptr;
@@ -54,7 +56,7 @@ bool solver_f_ok(int f, int solver) {
 }
 
 int implicit_lists(cumf_plan* p, ImplicitLists** out) {
-  if (p->implicit) {
+  if (p->implicit && p->implicit->built) {
     *out = p->implicit;
     return 0;
   }
@@ -84,7 +86,7 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
   host.insert(host.end(), item_dst.begin(), item_dst.end());
   host.insert(host.end(), mrow_dst.begin(), mrow_dst.end());
   host.insert(host.end(), empty.begin(), empty.end());
-  ImplicitLists* l = new ImplicitLists();
+  ImplicitLists* l = p->implicit ? p->implicit : new ImplicitLists();  // plan_free_lists may have made it
   l->n_long_items = n_long_items;
   l->n_long = (long)long_row.size();
   l->n_empty = (long)empty.size();
@@ -93,7 +95,12 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
     if (e == hipSuccess) e = hipMemcpy(l->d_block, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       fprintf(stderr, "HIP Error:\nFile = %s\nLine = %d\nReason = %s\n", __FILE__, __LINE__, hipGetErrorString(e));
-      free_implicit_lists(l);
+      if (l != p->implicit) {
+        free_implicit_lists(l);
+      } else if (l->d_block) {
+        (void)hipFree(l->d_block);
+        l->d_block = nullptr;
+      }
       return (int)e;
     }
     int* d = reinterpret_cast<int*>(l->d_block);
@@ -102,6 +109,7 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
     l->d_mrow_dst = l->d_item_dst + item_dst.size();
     l->d_empty_row = l->d_mrow_dst + mrow_dst.size();
   }
+  l->built = true;
   p->implicit = l;
   *out = l;
   return 0;
@@ -111,6 +119,10 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
 // consecutive) and is cut at the offsets 0, kFreeSeg, 2 kFreeSeg, ... from there, whatever the plan's own chunks.
 int free_lists(cumf_plan* p, ImplicitLists* l) {
   if (l->free_built) return 0;
+  if (l->d_free) {  // an earlier attempt failed half way
+    (void)hipFree(l->d_free);
+    l->d_free = nullptr;
+  }
   const size_t ni = (size_t)p->n_items, rows = (size_t)(p->row_end - p->row_begin);
   std::vector<int> row(ni), rowlen(ni);
   std::vector<long long> begin(ni);
@@ -214,19 +226,20 @@ ImplicitRoute implicit_route(const cumf_plan* p, int solver) {
 // The matrix-free half-iteration: done flags zeroed, then cg_iters + 1 passes (ImplicitFreeArgs); scratch from the pool.
 int update_matfree(cumf_plan* p, ImplicitLists* l, const int* colidx, const float* val, const float* gather, const float* G,
                    float* update, int f, float lambda, float alpha, int reg_mode, int cg_iters, hipStream_t s) {
-  int rc = free_lists(p, l);
+  FreeLists fl{};
+  int rc = plan_free_lists(p, &fl);
   if (rc) return rc;
   const long rows = p->row_end - p->row_begin;
   if (rows <= 0) return 0;
   ImplicitFreeArgs a{};
-  a.seg_row = l->d_seg_row;
-  a.seg_begin = l->d_seg_begin;
-  a.seg_len = l->d_seg_len;
-  a.row_seg0 = l->d_row_seg0;
-  a.row_nseg = l->d_row_nseg;
-  a.row_len = l->d_row_len;
+  a.seg_row = fl.seg_row;
+  a.seg_begin = fl.seg_begin;
+  a.seg_len = fl.seg_len;
+  a.row_seg0 = fl.row_seg0;
+  a.row_nseg = fl.row_nseg;
+  a.row_len = fl.row_len;
   a.rows = rows;
-  a.nseg = l->n_seg;
+  a.nseg = fl.n_seg;
   a.colidx = colidx;
   a.val = val;
   a.gather = gather;
@@ -253,6 +266,15 @@ int update_matfree(cumf_plan* p, ImplicitLists* l, const int* colidx, const floa
 }
 
 }  // namespace
+
+int cumf::plan_free_lists(cumf_plan* p, FreeLists* out) {
+  if (!p->implicit) p->implicit = new ImplicitLists();  // the long-row lists stay unbuilt until an implicit call wants them
+  ImplicitLists* l = p->implicit;
+  const int rc = free_lists(p, l);
+  if (rc) return rc;
+  *out = FreeLists{l->d_seg_row, l->d_seg_begin, l->d_seg_len, l->d_row_seg0, l->d_row_nseg, l->d_row_len, l->n_seg};
+  return 0;
+}
 
 int cumf::plan_empty_rows(cumf_plan* p, const int** rows, long* count) {
   ImplicitLists* l = nullptr;

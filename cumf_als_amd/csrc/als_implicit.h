@@ -70,6 +70,18 @@ hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* pa
 // into segments of at most kFreeSeg entries at fixed offsets from its start.
 constexpr int kFreeSeg = 2048;
 constexpr int kFreeRows = 32;  // rows per workgroup of the row pass
+// The segment lists of a plan (device arrays, rows indexed by row - row_begin), built once per plan at the first use by either
+// matrix-free route -- this one or the explicit one of als_free.cpp -- and freed with the plan.
+struct FreeLists {
+  const int* seg_row;          // n_seg: row of each segment
+  const long long* seg_begin;  // ... its first entry (index into colidx / val)
+  const int* seg_len;
+  const int* row_seg0;         // rows: first segment of each row (its segments are consecutive)
+  const int* row_nseg;
+  const int* row_len;          // stored entries of the row
+  long n_seg;
+};
+int plan_free_lists(cumf_plan* p, FreeLists* out);
 struct ImplicitFreeArgs {
   const int* seg_row;            // nseg: row of each segment
   const long long* seg_begin;    // ... its first entry (index into colidx / val)

@@ -312,6 +312,10 @@ enum {
   // biased ALS (als_bias.cpp): the residual ratings of a half-iteration, fp64 partial sums of the SSE and the mean
   kScratchBiasResid = 19,
   kScratchBiasPart = 20,
+  // matrix-free explicit CG (als_free.cpp): r | p, the segment partials of A v | b, r.r | done flags
+  kScratchFreeVec = 21,
+  kScratchFreePart = 22,
+  kScratchFreeWords = 23,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 // `count` elements of T (at least one) from the pool
