@@ -183,6 +183,22 @@ class Plan:
             pass
 
 
+def dual_rows_probe(rowptr, f: int, chunk: int, solver="lu", materialize: bool = False, gather_rows: int = 0,
+                    row_begin: int = 0, row_end: int | None = None) -> dict:
+    """Host only (cumf_dual_rows_probe): the whole rows a plan of `rowptr` with this chunk counts for the dual-form LU of
+    short rows -- of 1..79 ratings, of 1..95, without ratings -- and how many the route hands to it right now."""
+    rowptr = np.ascontiguousarray(rowptr)
+    if rowptr.dtype not in (np.int32, np.int64):
+        raise TypeError("rowptr must be int32 or int64")
+    rows = len(rowptr) - 1
+    info = (C.c_long * 4)()
+    _libmod.check(_libmod.load().cumf_dual_rows_probe(rowptr.ctypes.data_as(C.c_void_p), int(rowptr.dtype == np.int64), rows,
+                                                      row_begin, rows if row_end is None else row_end, int(f), int(chunk),
+                                                      _solver_id(solver), int(bool(materialize)), int(gather_rows), info),
+                  "cumf_dual_rows_probe")
+    return {"rows_1_79": int(info[0]), "rows_1_95": int(info[1]), "rows_empty": int(info[2]), "routed": int(info[3])}
+
+
 def update_fused(plan: Plan, colidx, val, gather, update, lambda_: float, solver="cg", cg_iters: int = 6):
     """One fused half-iteration over the plan's rows (cumf_als_update_fused)."""
     import torch

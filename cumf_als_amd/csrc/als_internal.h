@@ -132,6 +132,12 @@ struct PlanLists {
 constexpr int kShortRow = 32;
 bool short_cg_available(int f);
 hipError_t launch_short_cg(const KernelArgs& a, long n_items, hipStream_t stream);
+// Whole rows of 1 .. kDualMaxRow ratings have an LU route of their own on the n x n dual system (als_dual.hip, five tile blocks;
+// kDualMaxRow6: what a six-block instance would cover, counted by the plan, not built).  Plans list them behind every other
+// item (longest first) and in front of the rows without ratings.
+constexpr int kDualMaxRow = 79, kDualMaxRow6 = 95;
+bool dual_rows_available(int f);
+hipError_t launch_dual_rows(const KernelArgs& a, long n_items, hipStream_t stream);
 hipError_t launch_solve_batched(const float* A, const float* b, float* x, long batch, int f, int mode, int cg_iters,
                                 hipStream_t stream);
 // Gram arithmetic of the fused / materialising passes.
@@ -151,13 +157,14 @@ enum { kArithSplit3 = 0, kArithFast = 1, kArithPre = 2, kArithPrePk = 3, kArithS
 // ---- Routing of a half-iteration (als_route.cpp): which kernels, arithmetic and solvers a call runs on.
 // Every run-time knob that routes, read in one place.  gram / presplit: the environment (CUMF_ALS_GRAM,
 // CUMF_ALS_PRESPLIT) on first use, then what cumf_set_gram_mode / cumf_set_presplit set; presplit_mb, splitpk,
-// short_cg: the environment once per process; batched, wave_solve, lu_exact: the environment on every call.
+// short_cg: the environment once per process; dual, batched, wave_solve, lu_exact: the environment on every call.
 struct Switches {
   int gram;            // kGram*                       CUMF_ALS_GRAM = exact | fast | (split)
   int presplit;        // CUMF_PRESPLIT_*              CUMF_ALS_PRESPLIT = 0 | 1 | 2
   double presplit_mb;  // auto pre-split table cap     CUMF_ALS_PRESPLIT_MB (64)
   bool splitpk;        // kArithSplitPk wanted         CUMF_ALS_SPLITPK=0 turns it off
   bool short_cg;       // Gram-free CG of short rows   CUMF_ALS_SHORT_CG=0 turns it off
+  bool dual;           // dual-form LU of short rows   CUMF_ALS_DUAL=0 turns it off
   bool batched;        // two-wave path (f >= 112)     CUMF_ALS_NO_BATCHED turns it off
   bool wave_solve;     // wave CG of chunked rows      CUMF_ALS_NO_WAVE_SOLVE turns it off
   bool lu_exact;       // oracle-order batched LU      CUMF_ALS_LU_EXACT=1
@@ -173,6 +180,8 @@ struct PlanFacts {
   double chunk_share;  // share of the plan's ratings that sits in chunked rows
   long n_short;        // whole rows of at most kShortRow ratings (the last items)
   long gather_rows;    // rows of the gather table (cumf_plan_set_gather_rows), 0: unknown
+  long n_dual;         // whole rows of 1 .. kDualMaxRow ratings: the last items of the full and of the w list but for ...
+  long n_empty;        // ... the whole rows without ratings, the very last
 };
 enum Path {
   kPathNone,       // no fused kernel for (f, solver)
@@ -198,6 +207,9 @@ struct Route {
   Solve chunked;     // solver of the chunked rows
   Solve whole;       // solver of the whole rows
   bool sse;          // cumf_als_update_fused_sse covers every row
+  // LU on one wave, pre-split table: the n_dual whole rows in front of the last n_dual_behind (rows without ratings: they
+  // stay on the wave kernel) go to the dual-form kernel (als_dual.hip)
+  long n_dual, n_dual_behind;
 };
 Route route_for(int f, int mode, const PlanFacts& plan, const Switches& sw);
 hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& lists, hipStream_t stream);
@@ -352,6 +364,8 @@ struct cumf_plan {
   long long chunk_nnz = 0;  // ... of which in chunked rows
   long n_items = 0, n_slots = 0, n_mrows = 0;
   long n_short = 0;  // whole rows of at most kShortRow ratings: the last n_short items (and the last of the w list)
+  // whole rows of 1 .. kDualMaxRow / 1 .. kDualMaxRow6 ratings and without ratings: the item list and the w list end [.. | dual | empty]
+  long n_dual = 0, n_dual6 = 0, n_empty = 0;
   int* d_item_row = nullptr;
   long long* d_item_begin = nullptr;
   int* d_item_len = nullptr;

@@ -120,11 +120,33 @@ static hipError_t one_wave_items(const KernelArgs& a, int mode, const Route& r, 
     hipError_t e = launch_short_cg(as, r.n_short, stream);
     if (e != hipSuccess) return e;
   }
+  // Route::n_dual: the whole rows of 1 .. kDualMaxRow ratings, the last of the list but for the n_dual_behind rows without
+  // ratings, on their dual form -- first, like the short rows of the CG; the rows behind them in a wave launch of their own
+  // (the plan lists them there in the full list too: a combined launch of chunk items and whole rows hands them over alike)
+  const bool whole = r.chunk_first || L.n_mrows == 0;
+  const bool dual = r.n_dual > 0 && mode == kModeLU && !a.dense_slots && r.n_dual + r.n_dual_behind <= n_items;
+  long n_behind = 0;
+  if (dual) {
+    n_behind = r.n_dual_behind;
+    n_items -= r.n_dual + n_behind;
+    KernelArgs ad = aw;
+    ad.item_row += n_items, ad.item_begin += n_items, ad.item_len += n_items, ad.item_rowlen += n_items;
+    hipError_t e = launch_dual_rows(ad, r.n_dual, stream);
+    if (e != hipSuccess) return e;
+  }
   if (r.chunk_first) {
     hipError_t e = wave_items(chunk_items(a, L), mode, r, false, L.n_citems, stream);
     if (e != hipSuccess) return e;
   }
-  return wave_items(aw, mode, r, r.chunk_first || L.n_mrows == 0, n_items, stream);
+  if (n_behind > 0) {
+    const long at = n_items + r.n_dual;
+    KernelArgs ab = aw;
+    ab.item_row += at, ab.item_begin += at, ab.item_len += at, ab.item_rowlen += at;
+    if (ab.item_slot) ab.item_slot += at;
+    hipError_t e = wave_items(ab, mode, r, whole, n_behind, stream);
+    if (e != hipSuccess) return e;
+  }
+  return wave_items(aw, mode, r, whole, n_items, stream);
 }
 
 // Two-wave path (f >= 112): the Gram of every row is dumped as accumulator tiles (two waves per item,

@@ -47,6 +47,20 @@ int default_chunk(int f, long long nnz) {
   return (c / kStage) * kStage;
 }
 
+// Whole rows (at most `chunk` ratings) of [row_begin, row_end) by length: 1 .. kDualMaxRow, 1 .. kDualMaxRow6, none.  A row's
+// own length decides, so the batched plans of one side count what the unbatched plan counts.
+template <class RP>
+void count_dual_rows(const RP& rp, long row_begin, long row_end, int chunk, long* n_dual, long* n_dual6, long* n_empty) {
+  *n_dual = *n_dual6 = *n_empty = 0;
+  for (long u = row_begin; u < row_end; ++u) {
+    const long long len = rp(u + 1) - rp(u);
+    if (len > chunk) continue;
+    *n_empty += len == 0;
+    *n_dual += len >= 1 && len <= kDualMaxRow;
+    *n_dual6 += len >= 1 && len <= kDualMaxRow6;
+  }
+}
+
 }  // namespace
 
 extern "C" int cumf_plan_create(cumf_plan_t** out, const void* rowptr_host, int rowptr_is_64, long rows,
@@ -123,17 +137,22 @@ extern "C" int cumf_plan_create(cumf_plan_t** out, const void* rowptr_host, int 
   static const int order_mode = getenv("CUMF_ALS_ORDER") ? atoi(getenv("CUMF_ALS_ORDER")) : 0;
   // Round 6: whole rows of at most kShortRow ratings go behind everything else (longest first among themselves): the CG of
   // als_short.hip takes exactly the last n_short items of a launch; every other kernel treats items independently.
-  long n_short = 0;
+  // So do the whole rows of at most kDualMaxRow ratings, in front of them: the dual-form LU (als_dual.hip) takes the items in
+  // front of the rows without ratings, in the full list (a combined launch of chunk items and whole rows) as in the
+  // whole-row list -- a row is solved the same way whatever else its plan holds.
+  long n_short = 0, n_dual = 0, n_dual6 = 0, n_empty = 0;
   if (order_mode == 0) {
+    static_assert(kDualMaxRow >= kShortRow, "the short rows are the end of the tail");
     auto bucket = [&](size_t i) -> size_t {
-      const bool is_short = item_slot[i] < 0 && item_len[i] <= kShortRow;
-      return is_short ? (size_t)chunk + 1 + (size_t)(kShortRow - item_len[i]) : (size_t)(chunk - item_len[i]);
+      const bool is_tail = item_slot[i] < 0 && item_len[i] <= kDualMaxRow;
+      return is_tail ? (size_t)chunk + 1 + (size_t)(kDualMaxRow - item_len[i]) : (size_t)(chunk - item_len[i]);
     };
-    std::vector<long> start((size_t)chunk + kShortRow + 3, 0);
+    std::vector<long> start((size_t)chunk + kDualMaxRow + 3, 0);
     for (size_t i = 0; i < n_it; ++i) {
       ++start[bucket(i) + 1];  // bucket 0 = the longest
       n_short += item_slot[i] < 0 && item_len[i] <= kShortRow;
     }
+    count_dual_rows(rp, row_begin, row_end, chunk, &n_dual, &n_dual6, &n_empty);
     for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
     for (size_t i = 0; i < n_it; ++i) order[(size_t)start[bucket(i)]++] = (long)i;  // stable
   } else {
@@ -151,6 +170,7 @@ extern "C" int cumf_plan_create(cumf_plan_t** out, const void* rowptr_host, int 
   p->entry_begin = rp(row_begin);
   p->n_items = (long)n_it;
   p->n_short = n_short;
+  p->n_dual = n_dual, p->n_dual6 = n_dual6, p->n_empty = n_empty;
   p->n_slots = n_slots;
   p->n_mrows = (long)mrow_row.size();
   for (size_t i = 0; i < n_it; ++i) {
@@ -313,5 +333,44 @@ int cumf::plan_lists(const cumf_plan_t* p, PlanLists* out, hipStream_t stream, b
 
 PlanFacts cumf::plan_facts(const cumf_plan_t* p) {
   return PlanFacts{p->nb, p->n_mrows, p->n_citems, p->n_witems,
-                   p->plan_nnz > 0 ? (double)p->chunk_nnz / (double)p->plan_nnz : 0.0, p->n_short, p->gather_rows};
+                   p->plan_nnz > 0 ? (double)p->chunk_nnz / (double)p->plan_nnz : 0.0, p->n_short, p->gather_rows,
+                   p->n_dual, p->n_empty};
+}
+
+// Host only (no HIP call, no plan): what a plan of these rows would count for the dual-form route and what the route, with the
+// switches as they are now, would hand to it.
+extern "C" int cumf_dual_rows_probe(const void* rowptr_host, int rowptr_is_64, long rows, long row_begin, long row_end, int f,
+                                    int chunk, int solver, int materialize, long gather_rows, long info[4]) {
+  if (!rowptr_host || !info || rows < 0 || row_begin < 0 || row_end > rows || row_begin > row_end || f <= 0 || chunk < kStage)
+    return (int)hipErrorInvalidValue;
+  auto rp = [&](long i) -> long long {
+    return rowptr_is_64 ? static_cast<const long long*>(rowptr_host)[i]
+                        : static_cast<long long>(static_cast<const int*>(rowptr_host)[i]);
+  };
+  chunk = (chunk / kStage) * kStage;
+  PlanFacts facts{};
+  facts.nb = nb_for_f(f);
+  facts.gather_rows = gather_rows;
+  long long nnz = 0, chunk_nnz = 0;
+  for (long u = row_begin; u < row_end; ++u) {
+    const long long len = rp(u + 1) - rp(u);
+    nnz += len;
+    if (len <= chunk) {
+      ++facts.n_witems;
+      facts.n_short += len <= kShortRow;
+    } else {
+      ++facts.n_mrows;
+      facts.n_citems += (long)((len + chunk - 1) / chunk);
+      chunk_nnz += len;
+    }
+  }
+  facts.chunk_share = nnz > 0 ? (double)chunk_nnz / (double)nnz : 0.0;
+  long n_dual6 = 0;
+  count_dual_rows(rp, row_begin, row_end, chunk, &facts.n_dual, &n_dual6, &facts.n_empty);
+  const int mode = materialize ? kModeMaterialize : (solver == CUMF_SOLVER_LU ? kModeLU : kModeCG);
+  info[0] = facts.n_dual;
+  info[1] = n_dual6;
+  info[2] = facts.n_empty;
+  info[3] = route_for(f, mode, facts, switches()).n_dual;
+  return 0;
 }

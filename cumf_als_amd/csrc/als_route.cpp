@@ -29,12 +29,14 @@ Switches switches() {
   static const double presplit_mb = getenv("CUMF_ALS_PRESPLIT_MB") ? atof(getenv("CUMF_ALS_PRESPLIT_MB")) : 64.0;
   static const bool splitpk = !(getenv("CUMF_ALS_SPLITPK") && *getenv("CUMF_ALS_SPLITPK") == '0');
   static const bool short_cg = !getenv("CUMF_ALS_SHORT_CG") || atoi(getenv("CUMF_ALS_SHORT_CG")) != 0;
+  const char* dual = getenv("CUMF_ALS_DUAL");
   const char* lu_exact = getenv("CUMF_ALS_LU_EXACT");
   return Switches{g_gram_mode,
                   g_presplit_mode,
                   presplit_mb,
                   splitpk,
                   short_cg,
+                  !dual || atoi(dual) != 0,
                   !getenv("CUMF_ALS_NO_BATCHED"),
                   !getenv("CUMF_ALS_NO_WAVE_SOLVE"),
                   lu_exact && atoi(lu_exact) != 0};
@@ -73,6 +75,9 @@ static bool presplit_wanted(int f, long gather_rows, const Switches& sw) {
 //          86 % of the ratings) one combined launch stays: the whole rows fill the tail of the equal-sized chunk items
 //          (profiles/r05/stage_variants_ab.txt).
 //   short rows  CG plans on one wave, 32 <= f <= 128: the whole rows of at most kShortRow ratings never form their Gram.
+//   dual rows  LU plans on one wave in the production pre-split form (kArithPrePk, f = 96 .. 111): the whole rows of
+//          1 .. kDualMaxRow ratings (the plan lists them last in every item list) solve their n x n dual system
+//          (als_dual.hip).  Rows without ratings stay (the reference's NaN).  CUMF_ALS_DUAL=0: none.
 //   sse    every solver but two adds the train SSE of its rows: the workgroup CG of als_reduce_kernel, and its thread-grid LU
 //          below NB = 7 -- the chunked rows of LU plans below f = 96 and of CG plans at f = 112 .. 128 are not covered.
 Route route_for(int f, int mode, const PlanFacts& p, const Switches& sw) {
@@ -109,6 +114,12 @@ Route route_for(int f, int mode, const PlanFacts& p, const Switches& sw) {
                                                                                                           : kSolveInKernel;
   r.chunk_first = one && mode == kModeLU && p.n_mrows > 0 && p.n_citems > 0 && p.n_witems > 0 && p.chunk_share < 0.25;
   r.n_short = (one && mode == kModeCG && sw.short_cg && short_cg_available(f)) ? p.n_short : 0;
+  // the one-wave LU in the production pre-split form (never under CUMF_PRESPLIT_OFF / _VERIFY: those forms are compared bit
+  // for bit); the row's own length decides, not what else the plan holds (the WHOLE and the combined launch agree bit for bit)
+  const bool dual = one && mode == kModeLU && sw.dual && r.arith == kArithPrePk && nb == 7 && (f & 3) == 0 && f >= 96 &&
+                    dual_rows_available(f);
+  r.n_dual = dual ? p.n_dual : 0;
+  r.n_dual_behind = r.n_dual > 0 ? p.n_empty : 0;
   r.sse = wave && mode != kModeMaterialize &&
           (p.n_mrows == 0 || r.chunked == kSolveWaveCG || (mode == kModeLU && nb >= 7));
   return r;

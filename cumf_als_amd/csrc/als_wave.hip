@@ -470,6 +470,10 @@ static hipError_t launch_wave_lu_w(const KernelArgs& a, long n_items, hipStream_
   const size_t stage_lds = wave_stage_lds_floats<NB, ARITH>() * sizeof(float);
   const size_t lu_lds = wave_lu_lds_floats<NB>(a.f) * sizeof(float);
   const size_t lds = lu_lds > stage_lds ? lu_lds : stage_lds;
+  if (n_items <= 0) {  // every row of the plan went to the dual-form kernel (als_dual.hip): this is still the route's kernel
+    note_item_kernel(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>));
+    return hipSuccess;
+  }
   return launch_item_kernel(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>, dim3((unsigned)n_items), dim3(64), lds, stream, a);
 }
 // whole: no item of this launch dumps partial tiles (WHOLE: the instance without the dump exit)
@@ -502,7 +506,8 @@ static hipError_t launch_wave_fc(const KernelArgs& a, int mode, long n_items, hi
 
 template <int NB>
 hipError_t wave_item_launch(const KernelArgs& a, int mode, const Route& r, bool whole, long n_items, hipStream_t stream) {
-  if (n_items <= 0) return hipSuccess;
+  // (the one-wave LU is also called without items, to name its kernel: launch_wave_lu_w)
+  if (n_items <= 0 && !(mode == kModeLU && NB <= kMaxWaveNB && r.n_dual > 0)) return hipSuccess;
   if (mode != kModeMaterialize && mode != kModeLU && mode != kModeCG) return hipErrorInvalidValue;
   if constexpr (NB > kMaxWaveNB) {
     // two waves per item; items without a slot (whole rows) are solved in the kernel (CG, or the LU of

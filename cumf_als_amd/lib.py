@@ -32,6 +32,7 @@ C_ABI = {
     "cumf_plan_create": (_i, [_pvp, _vp, _i, _l, _l, _l, _i, _i]),
     "cumf_plan_destroy": (_i, [_vp]),
     "cumf_plan_info": (_i, [_vp, C.POINTER(_l)]),
+    "cumf_dual_rows_probe": (_i, [_vp, _i, _l, _l, _l, _i, _i, _i, _i, _l, C.POINTER(_l)]),
     "cumf_plan_set_gather_rows": (_i, [_vp, _l]),
     "cumf_gram_fast_status": (_i, [C.POINTER(_i)]),
     "cumf_fused_available": (_i, [_i, _i]),

@@ -72,6 +72,12 @@ int cumf_plan_create(cumf_plan_t** plan, const void* rowptr_host, int rowptr_is_
 int cumf_plan_destroy(cumf_plan_t* plan);
 /* counts for tests/diagnostics: [0]=items, [1]=partial slots, [2]=multi-chunk rows, [3]=chunk */
 int cumf_plan_info(const cumf_plan_t* plan, long info[4]);
+/* Host only (no GPU, no plan): what a plan of these rows with this chunk (>= 32) counts for the dual-form LU of short whole
+ * rows, and what the route hands to it with the switches as they are now (CUMF_ALS_DUAL, cumf_set_presplit,
+ * cumf_set_gram_mode).  info[0] = whole rows of 1 .. 79 ratings, [1] = of 1 .. 95, [2] = whole rows without ratings,
+ * [3] = rows the half-iteration (solver; materialize != 0: cumf_get_hermitian) would solve in dual form. */
+int cumf_dual_rows_probe(const void* rowptr_host, int rowptr_is_64, long rows, long row_begin, long row_end, int f,
+                         int chunk, int solver, int materialize, long gather_rows, long info[4]);
 
 /*
  * Fused half-iteration over the planned rows: RHS + Gram + solve in one pass,
