@@ -18,7 +18,6 @@ namespace cumf {
 // The plan lists its whole rows of at most kShortRow entries as the LAST n_short items; the items before them -- every chunk
 // and every longer whole row -- are the "long" items whose systems the CG route materialises into a compact batch.
 struct ImplicitLists {
-  bool built = false;     // the long-row / empty-row lists below (implicit_lists); the segments further down are built apart
   long n_long_items = 0;  // items [0, n_long_items) of the plan's list
   long n_long = 0;        // their rows, in the order of first appearance (longest first)
   long n_empty = 0;       // rows without stored entries
@@ -27,19 +26,11 @@ struct ImplicitLists {
   int* d_item_dst = nullptr;   // n_long_items: item -> compact index of its row
   int* d_mrow_dst = nullptr;   // n_mrows: chunked row -> compact index
   int* d_empty_row = nullptr;  // n_empty
-  // the segments and per-row lists of the matrix-free CGs (ImplicitFreeArgs, FreeArgs of als_free.h), built on first use
-  // (plan_free_lists); rows: row - row_begin
-  bool free_built = false;
-  long n_seg = 0;
-  char* d_free = nullptr;
-  long long* d_seg_begin = nullptr;
-  int *d_seg_row = nullptr, *d_seg_len = nullptr, *d_row_seg0 = nullptr, *d_row_nseg = nullptr, *d_row_len = nullptr;
 };
 
 void free_implicit_lists(ImplicitLists* l) {
   if (!l) return;
   if (l->d_block) (void)hipFree(l->d_block);
-  if (l->d_free) (void)hipFree(l->d_free);
   delete l;
 }
 
@@ -48,15 +39,13 @@ void free_implicit_lists(ImplicitLists* l) {
 namespace {
 
 bool implicit_f_ok(int f) { return f >= 8 && f <= 128 && (f % 2) == 0; }
-// the matrix-free CG, and the Gram and objective it needs
-bool matfree_f_ok(int f) { return f >= 8 && f <= 512 && (f % 2) == 0; }
 bool solver_f_ok(int f, int solver) {
   if (solver == CUMF_SOLVER_CG_MATFREE) return matfree_f_ok(f);
   return implicit_f_ok(f) && (solver == CUMF_SOLVER_CG || solver == CUMF_SOLVER_LU);
 }
 
 int implicit_lists(cumf_plan* p, ImplicitLists** out) {
-  if (p->implicit && p->implicit->built) {
+  if (p->implicit) {
     *out = p->implicit;
     return 0;
   }
@@ -86,7 +75,7 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
   host.insert(host.end(), item_dst.begin(), item_dst.end());
   host.insert(host.end(), mrow_dst.begin(), mrow_dst.end());
   host.insert(host.end(), empty.begin(), empty.end());
-  ImplicitLists* l = p->implicit ? p->implicit : new ImplicitLists();  // plan_free_lists may have made it
+  ImplicitLists* l = new ImplicitLists();
   l->n_long_items = n_long_items;
   l->n_long = (long)long_row.size();
   l->n_empty = (long)empty.size();
@@ -95,12 +84,7 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
     if (e == hipSuccess) e = hipMemcpy(l->d_block, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       fprintf(stderr, "HIP Error:\nFile = %s\nLine = %d\nReason = %s\n", __FILE__, __LINE__, hipGetErrorString(e));
-      if (l != p->implicit) {
-        free_implicit_lists(l);
-      } else if (l->d_block) {
-        (void)hipFree(l->d_block);
-        l->d_block = nullptr;
-      }
+      free_implicit_lists(l);
       return (int)e;
     }
     int* d = reinterpret_cast<int*>(l->d_block);
@@ -109,64 +93,8 @@ int implicit_lists(cumf_plan* p, ImplicitLists** out) {
     l->d_mrow_dst = l->d_item_dst + item_dst.size();
     l->d_empty_row = l->d_mrow_dst + mrow_dst.size();
   }
-  l->built = true;
   p->implicit = l;
   *out = l;
-  return 0;
-}
-
-// The segments of the plan's rows: a row of n entries starts where its first item does (a cut row's chunks are
-// consecutive) and is cut at the offsets 0, kFreeSeg, 2 kFreeSeg, ... from there, whatever the plan's own chunks.
-int free_lists(cumf_plan* p, ImplicitLists* l) {
-  if (l->free_built) return 0;
-  if (l->d_free) {  // an earlier attempt failed half way
-    (void)hipFree(l->d_free);
-    l->d_free = nullptr;
-  }
-  const size_t ni = (size_t)p->n_items, rows = (size_t)(p->row_end - p->row_begin);
-  std::vector<int> row(ni), rowlen(ni);
-  std::vector<long long> begin(ni);
-  if (ni) {
-    CUMF_HIP_CHECK(hipMemcpy(row.data(), p->d_item_row, ni * sizeof(int), hipMemcpyDeviceToHost));
-    CUMF_HIP_CHECK(hipMemcpy(rowlen.data(), p->d_item_rowlen, ni * sizeof(int), hipMemcpyDeviceToHost));
-    CUMF_HIP_CHECK(hipMemcpy(begin.data(), p->d_item_begin, ni * sizeof(long long), hipMemcpyDeviceToHost));
-  }
-  std::vector<long long> start(rows, -1);
-  std::vector<int> len(rows, 0);
-  for (size_t i = 0; i < ni; ++i) {
-    const size_t u = (size_t)(row[i] - p->row_begin);
-    if (start[u] < 0 || begin[i] < start[u]) start[u] = begin[i];
-    len[u] = rowlen[i];
-  }
-  std::vector<long long> seg_begin;
-  std::vector<int> seg_row, seg_len, row_seg0(rows), row_nseg(rows);
-  for (size_t u = 0; u < rows; ++u) {
-    row_seg0[u] = (int)seg_row.size();
-    for (int o = 0; o < len[u]; o += kFreeSeg) {
-      seg_begin.push_back(start[u] + o);
-      seg_row.push_back((int)u);
-      seg_len.push_back(len[u] - o < kFreeSeg ? len[u] - o : kFreeSeg);
-    }
-    row_nseg[u] = (int)seg_row.size() - row_seg0[u];
-  }
-  const size_t ns = seg_row.size();
-  std::vector<int> ints;
-  for (auto* v : {&seg_row, &seg_len, &row_seg0, &row_nseg, &len}) ints.insert(ints.end(), v->begin(), v->end());
-  const size_t bytes = ns * sizeof(long long) + ints.size() * sizeof(int);
-  if (bytes) {
-    CUMF_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&l->d_free), bytes));
-    if (ns) CUMF_HIP_CHECK(hipMemcpy(l->d_free, seg_begin.data(), ns * sizeof(long long), hipMemcpyHostToDevice));
-    CUMF_HIP_CHECK(hipMemcpy(l->d_free + ns * sizeof(long long), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
-    l->d_seg_begin = reinterpret_cast<long long*>(l->d_free);
-    int* d = reinterpret_cast<int*>(l->d_free + ns * sizeof(long long));
-    l->d_seg_row = d;
-    l->d_seg_len = d + ns;
-    l->d_row_seg0 = d + 2 * ns;
-    l->d_row_nseg = l->d_row_seg0 + rows;
-    l->d_row_len = l->d_row_nseg + rows;
-  }
-  l->n_seg = (long)ns;
-  l->free_built = true;
   return 0;
 }
 
@@ -223,58 +151,18 @@ ImplicitRoute implicit_route(const cumf_plan* p, int solver) {
   return ImplicitRoute{false, false, p->n_short};
 }
 
-// The matrix-free half-iteration: done flags zeroed, then cg_iters + 1 passes (ImplicitFreeArgs); scratch from the pool.
-int update_matfree(cumf_plan* p, ImplicitLists* l, const int* colidx, const float* val, const float* gather, const float* G,
-                   float* update, int f, float lambda, float alpha, int reg_mode, int cg_iters, hipStream_t s) {
-  FreeLists fl{};
-  int rc = plan_free_lists(p, &fl);
-  if (rc) return rc;
-  const long rows = p->row_end - p->row_begin;
-  if (rows <= 0) return 0;
+// The matrix-free half-iteration: the driver of als_free.cpp on the implicit kernels, with the scratch kinds of this file.
+int update_matfree(cumf_plan* p, const int* colidx, const float* val, const float* gather, const float* G, float* update,
+                   float lambda, float alpha, int reg_mode, int cg_iters, hipStream_t s) {
   ImplicitFreeArgs a{};
-  a.seg_row = fl.seg_row;
-  a.seg_begin = fl.seg_begin;
-  a.seg_len = fl.seg_len;
-  a.row_seg0 = fl.row_seg0;
-  a.row_nseg = fl.row_nseg;
-  a.row_len = fl.row_len;
-  a.rows = rows;
-  a.nseg = fl.n_seg;
-  a.colidx = colidx;
-  a.val = val;
-  a.gather = gather;
   a.G = G;
-  a.x = update + (size_t)p->row_begin * f;
-  a.f = f;
-  a.lambda = lambda;
   a.alpha = alpha;
   a.reg_mode = reg_mode;
-  float *vec = nullptr, *part = nullptr, *words = nullptr;
-  if ((rc = scratch(s, kScratchImpTT, 2 * (size_t)rows * f, &vec)) ||
-      (rc = scratch(s, kScratchImpSlots, 2 * (size_t)a.nseg * f, &part)) || (rc = scratch(s, kScratchImpX, 2 * (size_t)rows, &words)))
-    return rc;
-  a.r = vec;
-  a.p = vec + (size_t)rows * f;
-  a.part = part;
-  a.bpart = part + (size_t)a.nseg * f;
-  a.rs = words;
-  a.done = reinterpret_cast<int*>(words + rows);
-  CUMF_HIP_CHECK(hipMemsetAsync(a.done, 0, (size_t)rows * sizeof(int), s));
-  const int steps = cg_iters > 0 ? cg_iters : 0;
-  for (int k = 0; k <= steps; ++k) CUMF_HIP_CHECK(launch_implicit_free_pass(a, k, steps, s));
-  return 0;
+  return run_matfree(p, &a, colidx, val, gather, update, lambda, cg_iters, kScratchImpTT, kScratchImpSlots, kScratchImpX, s,
+                     [&](int step, int steps) { return launch_implicit_free_pass(a, step, steps, s); });
 }
 
 }  // namespace
-
-int cumf::plan_free_lists(cumf_plan* p, FreeLists* out) {
-  if (!p->implicit) p->implicit = new ImplicitLists();  // the long-row lists stay unbuilt until an implicit call wants them
-  ImplicitLists* l = p->implicit;
-  const int rc = free_lists(p, l);
-  if (rc) return rc;
-  *out = FreeLists{l->d_seg_row, l->d_seg_begin, l->d_seg_len, l->d_row_seg0, l->d_row_nseg, l->d_row_len, l->n_seg};
-  return 0;
-}
 
 int cumf::plan_empty_rows(cumf_plan* p, const int** rows, long* count) {
   ImplicitLists* l = nullptr;
@@ -362,7 +250,7 @@ extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const ImplicitRoute r = implicit_route(p, solver);
   ScratchLease lease;
-  if (r.matfree) return update_matfree(p, l, colidx, val, gather, G, update, f, lambda, alpha, reg_mode, cg_iters, s);
+  if (r.matfree) return update_matfree(p, colidx, val, gather, G, update, lambda, alpha, reg_mode, cg_iters, s);
   ImplicitArgs a = base_implicit_args(p, colidx, val, gather, G, f, lambda, alpha, reg_mode);
   a.update = update;
   a.cg_iters = cg_iters;

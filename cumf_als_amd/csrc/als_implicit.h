@@ -3,6 +3,7 @@
 #ifndef CUMF_ALS_IMPLICIT_H_
 #define CUMF_ALS_IMPLICIT_H_
 
+#include "als_free.h"  // FreeArgs, which ImplicitFreeArgs extends
 #include "als_internal.h"
 
 namespace cumf {
@@ -66,47 +67,14 @@ inline long implicit_gram_slab(int f) {
 }
 // The Gram partials of a table with 128 < f <= 512 (als_implicit_free.hip; launch_implicit_gram reduces them)
 hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* part, hipStream_t stream);
-// The matrix-free CG (als_implicit_free.hip): rows are the plan's, indexed by row - row_begin; a row's stored entries are cut
-// into segments of at most kFreeSeg entries at fixed offsets from its start.
-constexpr int kFreeSeg = 2048;
+// The matrix-free CG (als_implicit_free.hip): the arguments and segments of als_free.h, plus G and the confidence weights.
 constexpr int kFreeRows = 32;  // rows per workgroup of the row pass
-// The segment lists of a plan (device arrays, rows indexed by row - row_begin), built once per plan at the first use by either
-// matrix-free route -- this one or the explicit one of als_free.cpp -- and freed with the plan.
-struct FreeLists {
-  const int* seg_row;          // n_seg: row of each segment
-  const long long* seg_begin;  // ... its first entry (index into colidx / val)
-  const int* seg_len;
-  const int* row_seg0;         // rows: first segment of each row (its segments are consecutive)
-  const int* row_nseg;
-  const int* row_len;          // stored entries of the row
-  long n_seg;
-};
-int plan_free_lists(cumf_plan* p, FreeLists* out);
-struct ImplicitFreeArgs {
-  const int* seg_row;            // nseg: row of each segment
-  const long long* seg_begin;    // ... its first entry (index into colidx / val)
-  const int* seg_len;
-  const int* row_seg0;           // rows: first segment of each row (its segments are consecutive)
-  const int* row_nseg;
-  const int* row_len;            // stored entries of the row (0: x = 0)
-  long long rows, nseg;
-  const int* colidx;
-  const float* val;
-  const float* gather;
-  const float* G;
-  float* x;      // update + row_begin * f: warm start in, solution out
-  float* r;      // rows x f residuals
-  float* p;      // rows x f search directions
-  float* part;   // nseg x f: T^T (w o T v) of each segment
-  float* bpart;  // nseg x f: the segment's part of b (first pass)
-  float* rs;     // rows: r.r
-  int* done;     // rows: 1 once the row's CG has ended (zeroed before the first pass)
-  int f;
-  float lambda, alpha;
+struct ImplicitFreeArgs : FreeArgs {
+  const float* G;  // f x f Gram of `gather`
+  float alpha;
   int reg_mode;
 };
-// step 0: the sparse pass with v = x (and b), then r = b - A x, p = r; step k >= 1: CG step k with A p.  step == cg_iters: the
-// last pass.
+// the passes of launch_free_pass, on the implicit kernels
 hipError_t launch_implicit_free_pass(const ImplicitFreeArgs& a, int step, int cg_iters, hipStream_t stream);
 
 // The plan's rows without stored entries (absolute row ids, device array) from the lists of als_implicit.cpp, built on

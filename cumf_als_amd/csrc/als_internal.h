@@ -352,6 +352,10 @@ struct ScratchLease {
 // Work lists of the implicit-feedback half-iterations, built on a plan at first use and freed with it (als_implicit.cpp).
 struct ImplicitLists;
 void free_implicit_lists(ImplicitLists* lists);
+// The row segments of the matrix-free CGs, explicit and implicit, built on a plan at first use and freed with it (als_free.h,
+// als_free.cpp).
+struct FreeSegLists;
+void free_seg_lists(FreeSegLists* lists);
 
 }  // namespace cumf
 
@@ -388,6 +392,8 @@ struct cumf_plan {
   long gather_rows = 0;
   // implicit feedback: the long-row / empty-row lists of als_implicit.cpp (built on first use, freed with the plan)
   cumf::ImplicitLists* implicit = nullptr;
+  // matrix-free CG, explicit and implicit: the row segments of als_free.cpp (built on first use, freed with the plan)
+  cumf::FreeSegLists* free_seg = nullptr;
 };
 
 namespace cumf {

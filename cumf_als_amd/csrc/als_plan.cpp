@@ -266,6 +266,7 @@ extern "C" int cumf_plan_destroy(cumf_plan_t* p) {
   if (p->d_block) (void)hipFree(p->d_block);  // every index array lives in this one block
   if (p->d_part) (void)hipFree(p->d_part);
   free_implicit_lists(p->implicit);
+  free_seg_lists(p->free_seg);
   delete p;
   return 0;
 }

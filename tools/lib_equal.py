@@ -1,6 +1,7 @@
 """Are two builds of the library bit-identical on a half-iteration?
     python tools/lib_equal.py libA libB [f] [solver] [scale] [gram mode] [presplit]
-Each library runs in its own process (CUMF_ALS_LIB, other CUMF_ALS_* switches inherited), one after the other, for at most
+solver: one of ALSEngine's, or implicit:SOLVER:REG for ImplicitALSEngine(solver=SOLVER, alpha=40, reg=REG), e.g.
+implicit:cg_matfree:plain (the same factors are hashed; no SSE bins).  Each library runs in its own process (CUMF_ALS_LIB, other CUMF_ALS_* switches inherited), one after the other, for at most
 LIB_EQUAL_TIMEOUT seconds (300) each; libB is not started if libA's process failed, died on a signal or ran out of time.  The
 factors after two iterations on the Netflix shape (scaled by `scale`) and the fused train-SSE bins of one more Theta update ("-"
 where the plans cannot deliver them) are compared bit for bit, and so is the name of the last Gram kernel.  Also printed: the
@@ -18,13 +19,16 @@ als.set_gram_mode(gram)
 als.set_presplit(presplit)
 shp = datagen.SHAPES["netflix"]
 r = datagen.synth_ratings(int(shp["m"] * scale), int(shp["n"] * scale), int(shp["nnz"] * scale * scale), 1000, seed=0, device="cuda")
-eng = als.ALSEngine(r, f, shp["lam"], solver=solver)
+if solver.startswith("implicit:"):  # implicit:SOLVER:REG
+    eng = als.ImplicitALSEngine(r, f, shp["lam"], 40.0, solver=solver.split(":")[1], reg=solver.split(":")[2])
+else:
+    eng = als.ALSEngine(r, f, shp["lam"], solver=solver)
 eng.init_factors()
 eng.iterate(2)
 name = als.last_kernel_name().replace(" ", "")
 h = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]
 sse = "-"
-if eng.fused and all(als.fused_sse_available(p, solver) for p in eng.t_plans):
+if getattr(eng, "fused", False) and all(als.fused_sse_available(p, solver) for p in eng.t_plans):  # (not the implicit engine)
     bins = torch.zeros(als.SSE_BINS, dtype=torch.float64, device="cuda")
     for p in eng.t_plans:
         als.update_fused_sse(p, r.csc_indices, r.csc_data, eng.XT, eng.thetaT, eng.lam, solver, eng.cg_iters, bins)
