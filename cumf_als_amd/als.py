@@ -24,6 +24,8 @@
   tables and residual ratings; `BiasedALSEngine` trains it, and ranks and evaluates by the biased prediction.
 * `update_matfree`, `matfree_available` (include/cumf_free_capi.h): the explicit half-iteration at any even 8 <= f <= 512 by a
   CG that never forms a row's system; `ALSEngine(solver="cg_matfree")` and `do_als(solver="cg_matfree")` train with it.
+* `update_weighted`, `weighted_loss`, `weighted_available` (include/cumf_weighted_capi.h): the same CG with a weight on every
+  stored entry and one weight w0 on everything unstored; `WeightedALSEngine` trains with it.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -1082,6 +1084,120 @@ class ImplicitALSEngine(_Engine):
         """The implicit objective of the current factors (fp64)."""
         return float(implicit_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.XT, self.thetaT, self.lam,
                                    self.alpha, self.reg).item())
+
+
+# ---------------------------------------------------------------------------------------
+# weighted ALS (include/cumf_weighted_capi.h)
+# ---------------------------------------------------------------------------------------
+
+def weighted_available(f: int) -> bool:
+    """cumf_weighted_available: weighted ALS takes even 8 <= f <= 512."""
+    return bool(_libmod.load().cumf_weighted_available(int(f)))
+
+
+def _check_w0(w0) -> float:
+    w0 = float(w0)
+    if not w0 >= 0.0:  # (NaN too)
+        raise ValueError(f"w0, the weight of the unstored entries, must be >= 0 (got {w0})")
+    return w0
+
+
+def update_weighted(plan: Plan, colidx, val, wgt, gather, G, update, lambda_: float, w0: float = 0.0, reg="weighted",
+                    cg_iters: int = 6):
+    """One weighted half-iteration over the plan's rows that never forms a system (cumf_als_update_weighted): stored entry e
+    has the rating val[e] and the weight wgt[e] >= 0, every unstored entry the target 0 and the weight w0 >= 0.  The CG of
+    `update_matfree` -- warm start from `update`, at most `cg_iters` steps, exit when r.r < 1e-4 -- on
+    A v = w0 G v + T^T ((w - w0) o (T v)) + reg v; even 8 <= f <= 512.  G is implicit_gram(gather), read only when w0 > 0
+    (None is fine at w0 = 0); reg "weighted" (lambda n_u) or "plain" (lambda).  Rows without entries get 0."""
+    import torch
+
+    if not weighted_available(plan.f):
+        raise ValueError(f"update_weighted takes even 8 <= f <= 512 (got f = {plan.f})")
+    w0 = _check_w0(w0)
+    if w0 > 0 and G is None:
+        raise ValueError(f"update_weighted: w0 = {w0} > 0 needs G = implicit_gram(gather)")
+    if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
+        raise ValueError(f"update_weighted: gather and update must be [rows, {plan.f}], the plan's f "
+                         f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
+    if G is not None and tuple(G.shape) != (plan.f, plan.f):
+        raise ValueError(f"update_weighted: G must be [{plan.f}, {plan.f}] (got {tuple(G.shape)})")
+    if wgt.shape != val.shape:
+        raise ValueError(f"update_weighted: wgt must be parallel to val (got {tuple(wgt.shape)}, {tuple(val.shape)})")
+    _libmod.check(_libmod.load().cumf_als_update_weighted(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32), _dp(gather, torch.float32),
+        _dp(G, torch.float32), _dp(update, torch.float32), float(lambda_), w0, _reg_id(reg), int(cg_iters), _stream()),
+        "cumf_als_update_weighted")
+    return update
+
+
+def weighted_loss(rowptr, colidx, val, wgt, XT, thetaT, lambda_: float, w0: float = 0.0, reg="weighted", out=None):
+    """The weighted objective (cumf_weighted_loss) as a 1-element fp64 tensor: sum_stored w (r - x.y)^2 + w0 sum_unstored
+    (x.y)^2 + the regularisers; rowptr/colidx/val/wgt are the CSR arrays on the device (rowptr int32), XT m x f,
+    thetaT n x f."""
+    import torch
+
+    m, f = int(XT.shape[0]), int(XT.shape[1])
+    if out is None:
+        out = torch.zeros(1, dtype=torch.float64, device=XT.device)
+    _libmod.check(_libmod.load().cumf_weighted_loss(
+        _dp(rowptr, torch.int32), _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32),
+        _dp(XT, torch.float32), _dp(thetaT, torch.float32), m, int(thetaT.shape[0]), f, float(lambda_), _check_w0(w0),
+        _reg_id(reg), _dp(out, torch.float64), _stream()), "cumf_weighted_loss")
+    return out
+
+
+class WeightedALSEngine(_Engine):
+    """Weighted ALS on one GPU: rating r_ui of `r` (a `datagen.Ratings` on the device) counts with the weight w_ui >= 0 of
+    `weights` (a device tensor parallel to r.csr_data, CSR entry order), every unstored entry is a target of 0 with the weight
+    w0 >= 0.  Same shape as `ALSEngine`; every half-iteration is `update_weighted` (even 8 <= f <= 512, CG only), and with
+    w0 > 0 it forms G = Y^T Y of the fixed side once, before its batches.  reg "weighted" (lambda n_u, the default) or "plain".
+    w = 1, w0 = 0 is ALSEngine(solver="cg_matfree"); w = 1 + alpha |r| on ratings (r > 0) with w0 = 1 is
+    ImplicitALSEngine(solver="cg_matfree")."""
+
+    def __init__(self, r, weights, f: int, lambda_: float, w0: float = 0.0, reg="weighted", cg_iters: int = 6,
+                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0):
+        import torch
+
+        if not weighted_available(f):
+            raise ValueError(f"weighted ALS takes even 8 <= f <= 512 (got f = {f})")
+        self.lam, self.w0 = float(lambda_), _check_w0(w0)
+        self.reg, self.cg_iters = _reg_id(reg), int(cg_iters)
+        dev = r.csr_indices.device
+        if not hasattr(weights, "is_cuda") or weights.device != dev or weights.dtype != torch.float32 \
+                or tuple(weights.shape) != tuple(r.csr_data.shape):
+            raise TypeError("weights must be a float32 tensor on the ratings' device, parallel to r.csr_data")
+        if not bool((torch.isfinite(weights) & (weights >= 0)).all()):
+            raise ValueError("weights must be finite and >= 0")
+        super().__init__(r, f, x_batch, theta_batch, chunk)
+        self.w_csr = weights.contiguous()
+        # the CSC-order copy: CSR entry e = (row, col) sits at the rank of col * m + row, which a stable sort delivers; checked
+        # against the dataset's own CSC arrays bit for bit, so a dataset whose two orders disagree cannot train silently
+        key = r.csr_indices.to(torch.int64) * r.m + r.coo_row.to(torch.int64)
+        perm = torch.sort(key, stable=True).indices
+        if not (torch.equal(r.csr_data[perm].view(torch.int32), r.csc_data.view(torch.int32))
+                and torch.equal(r.coo_row[perm].to(torch.int32), r.csc_indices.to(torch.int32))):
+            raise ValueError("the dataset's CSC arrays are not its CSR entries sorted by (column, row): cannot place the "
+                             "weights in CSC order")
+        self.w_csc = self.w_csr[perm].contiguous()
+        self.csr_rowptr = r.csr_indptr.to(device=self.device, dtype=torch.int32).contiguous()
+        self.G = torch.empty((f, f), dtype=torch.float32, device=self.device) if self.w0 > 0 else None
+
+    def _half_weighted(self, plans, colidx, val, wgt, gather, update):
+        if self.w0 > 0:
+            implicit_gram(gather, self.G)
+        for p in plans:
+            update_weighted(p, colidx, val, wgt, gather, self.G, update, self.lam, self.w0, self.reg, self.cg_iters)
+
+    def update_x(self):
+        self._half_weighted(self.x_plans, self.r.csr_indices, self.r.csr_data, self.w_csr, self.thetaT, self.XT)
+
+    def update_theta(self):
+        self._half_weighted(self.t_plans, self.r.csc_indices, self.r.csc_data, self.w_csc, self.XT, self.thetaT)
+
+    def loss(self) -> float:
+        """The weighted objective of the current factors (fp64)."""
+        return float(weighted_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.w_csr, self.XT, self.thetaT,
+                                   self.lam, self.w0, self.reg).item())
 
 
 # ---------------------------------------------------------------------------------------

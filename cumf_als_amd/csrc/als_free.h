@@ -24,6 +24,8 @@ inline bool matfree_f_ok(int f) { return f >= 8 && f <= 512 && (f % 2) == 0; }
 // Rows are the plan's, indexed by row - row_begin; a row's stored entries are cut into segments of at most kFreeSeg entries
 // at fixed offsets from its start.
 constexpr int kFreeSeg = 2048;
+constexpr int kFreeRows = 32;  // rows per workgroup of a row pass that adds G v (als_free_core.h: free_gram_rows)
+constexpr int kFreeRegPlain = 1;  // ... and its reg mode with reg_u = lambda (CUMF_IMPLICIT_REG_PLAIN); else (float)n_u lambda
 // The segment lists of a plan (device arrays), built once per plan at the first use by either route (cumf_plan::free_seg) and
 // freed with the plan (free_seg_lists, als_internal.h).
 struct FreeSegLists {

@@ -14,7 +14,7 @@ namespace cumf {
 
 template <int Q>
 __global__ __launch_bounds__(kFreeThreads) void free_sparse_kernel(const FreeArgs a, int first) {
-  free_sparse_pass<Q, false>(a, first, 0.f);
+  free_sparse_pass<Q, kFreeWeightNone>(a, first, 0.f);
 }
 
 template <int Q>

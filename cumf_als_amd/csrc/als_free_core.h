@@ -1,10 +1,13 @@
-// als_free_core.h -- the device core of the two matrix-free CGs: the explicit one (als_free.hip: A_u v = T_u^T (T_u v) + reg v)
-// and the implicit one (als_implicit_free.hip: A_u v = G v + T_u^T (w o (T_u v)) + reg v).  T_u is the row's gathered block of
-// factor rows.  The kernels of both files are wrappers around
+// als_free_core.h -- the device core of the matrix-free CGs: the explicit one (als_free.hip: A_u v = T_u^T (T_u v) + reg v),
+// the implicit one (als_implicit_free.hip: A_u v = G v + T_u^T (w o (T_u v)) + reg v) and the weighted one (als_weighted.hip:
+// A_u v = w0 G v + T_u^T ((w - w0) o (T_u v)) + reg v).  T_u is the row's gathered block of factor rows.  The kernels of the
+// three files are wrappers around
 //   free_sparse_pass  one wave per SEGMENT of a row (at most kFreeSeg entries, cut at fixed offsets from the row's start): per
-//                     block of N entries s = T v by the transposing wave reduction, then T^T s (kWeighted: T^T (w o s))
+//                     block of N entries s = T v by the transposing wave reduction, then T^T s (with weights: T^T (w o s))
 //                     accumulated in entry order, written as one f-vector partial per segment; the first pass of a
 //                     half-iteration also writes the segment's part of b;
+//   free_gram_rows    kFreeRows rows per workgroup: their vectors staged in LDS and G v of all of them on the matrix pipe, then
+//                     free_row_update of each live row;
 //   free_row_update   one wave on one live row: sums the segment partials in segment order, adds reg v (kGram: and the row's
 //                     G v) and runs the CG scalar and vector updates of cumf_cg_solve_batched (exit when r.r < 1e-4, a done
 //                     flag per row).
@@ -23,10 +26,15 @@ constexpr int kFreeThreads = 256;  // four waves
 
 // ---- the sparse pass: lane l holds features l + 64 q (q < Q = ceil(f / 64)) of every vector.
 // first: v = x (the warm start) and the segment's part of b is written too; otherwise v = p.
-// kWeighted: entry e carries the confidence weight w = alpha |val| and the coefficient (val > 0 ? 1 + w : 0) in b; otherwise
-// no weight and the coefficient val.
-template <int Q, bool kWeighted>
-__device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, float alpha) {
+// Where entry e takes its weight in T^T (w o s) and its coefficient in b from:
+//   kFreeWeightNone   no weight, coefficient val;
+//   kFreeWeightAlpha  the confidence weight w = wpar |val| (wpar = alpha), coefficient (val > 0 ? 1 + w : 0);
+//   kFreeWeightArray  w = wgt[e] - wpar (wpar = w0, the weight of the unstored entries), coefficient wgt[e] val; wgt is
+//                     indexed as val.
+enum FreeWeight { kFreeWeightNone = 0, kFreeWeightAlpha = 1, kFreeWeightArray = 2 };
+template <int Q, FreeWeight kWeight>
+__device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, float wpar, const float* wgt = nullptr) {
+  constexpr bool kWeighted = kWeight != kFreeWeightNone;
   constexpr int N = Q <= 4 ? 16 : 8;  // entries per block: N x Q <= 64 gathered values per lane (N = 32: SGPR spills)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -49,11 +57,15 @@ __device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, fl
       const bool live = lane < cnt64;
       const int jl = live ? a.colidx[begin + s + lane] : 0;
       const float rl = live ? a.val[begin + s + lane] : 0.f;
-      [[maybe_unused]] float wl = 0.f;  // confidence weight of entry s + lane
+      [[maybe_unused]] float wl = 0.f;  // weight of entry s + lane
       float cl = rl;                    // its coefficient in b
-      if constexpr (kWeighted) {
-        wl = live ? alpha * fabsf(rl) : 0.f;
+      if constexpr (kWeight == kFreeWeightAlpha) {
+        wl = live ? wpar * fabsf(rl) : 0.f;
         cl = (live && rl > 0.f) ? 1.f + wl : 0.f;
+      } else if constexpr (kWeight == kFreeWeightArray) {
+        const float gl = live ? wgt[begin + s + lane] : 0.f;
+        wl = live ? gl - wpar : 0.f;
+        cl = gl * rl;
       }
       for (int b = 0; b < cnt64; b += N) {
         const int cnt = cnt64 - b < N ? cnt64 - b : N;  // uniform
@@ -184,6 +196,67 @@ __device__ __forceinline__ void free_row_update(const FreeArgs a, long long row,
       }
       if (lane == 0) a.rs[row] = rsnew;
     }
+  }
+}
+
+// ---- the row pass with G v: kFreeRows rows per workgroup of kFreeThreads.  mode 0 (after the first sparse pass):
+// r = b - A x, p = r, rs = r.r; mode 1: one CG step with A p.  last: the rows are done after this pass.  Args: FreeArgs
+// extended by G (the f x f Gram of `gather`) and reg_mode (kFreeRegPlain: reg = lambda, else (float)n lambda).  kScale: G v is multiplied by gscale as it leaves the accumulators (the weighted
+// route's w0; at gscale = 1 the product is the factor itself, bit for bit).
+template <int Q, bool kScale, class Args>
+__device__ __forceinline__ void free_gram_rows(const Args& a, float gscale, int mode, int last) {
+  constexpr int P = 64 * Q + 4;  // LDS pitch: the 16 rows one MFMA operand reads start 4 banks apart
+  __shared__ float vs[kFreeRows * P];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int f = a.f, FT = (f + 15) / 16, FP = 16 * FT;
+  const long long r0 = (long long)blockIdx.x * kFreeRows;
+  const int nr = (int)(a.rows - r0 < kFreeRows ? a.rows - r0 : kFreeRows);
+  if (!__syncthreads_or((int)threadIdx.x < nr && !a.done[r0 + threadIdx.x])) return;  // every row of the block is done
+  const float* V = mode == 0 ? a.x : a.p;
+  for (int e = threadIdx.x; e < kFreeRows * FP; e += kFreeThreads) {
+    const int rr = e / FP, c = e - rr * FP;
+    vs[rr * P + c] = (rr < nr && c < f) ? V[(size_t)(r0 + rr) * f + c] : 0.f;
+  }
+  __syncthreads();
+  // G v of the block's rows: wave w takes the 16-column tiles J = w + 4 t of both 16-row tiles; v_mfma_f32_16x16x4_f32 with
+  // A[i][k] = v_i[k] (LDS) and B[k][j] = G[k][16 J + j] (G symmetric, read from L2)
+  f32x4 acc[Q][2];
+#pragma unroll
+  for (int t = 0; t < Q; ++t) acc[t][0] = acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kk = 0; kk < FP / 4; ++kk) {
+    const int k = 4 * kk + (lane >> 4);
+    const float a0 = vs[(lane & 15) * P + k], a1 = vs[(16 + (lane & 15)) * P + k];
+#pragma unroll
+    for (int t = 0; t < Q; ++t) {
+      const int J = wave + 4 * t;
+      if (J < FT) {  // uniform
+        const int c = 16 * J + (lane & 15);
+        const float g = (k < f && c < f) ? a.G[(size_t)k * f + c] : 0.f;
+        acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, g, acc[t][0], 0, 0, 0);
+        acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, g, acc[t][1], 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < Q; ++t) {
+    const int J = wave + 4 * t;
+    if (J < FT) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          vs[(16 * h + 4 * (lane >> 4) + r) * P + 16 * J + (lane & 15)] = kScale ? acc[t][h][r] * gscale : acc[t][h][r];
+    }
+  }
+  __syncthreads();
+  for (int rr = wave; rr < nr; rr += 4) {
+    const long long row = r0 + rr;
+    if (a.done[row]) continue;  // uniform
+    const int n = a.row_len[row];
+    const float reg = a.reg_mode == kFreeRegPlain ? a.lambda : (float)n * a.lambda;
+    free_row_update<Q, true>(a, row, n, reg, vs + rr * P, lane, mode, last);
   }
 }
 

@@ -10,7 +10,7 @@ namespace cumf {
 
 constexpr int kImpGramSlab = 1024;    // table rows per workgroup of the Gram kernel (one fp32 partial each)
 constexpr int kImpLossBlocks = 1024;  // workgroups of the loss pass (one fp64 partial each)
-constexpr int kImpRegPlain = 1;       // CUMF_IMPLICIT_REG_PLAIN (reg_u = lambda); else lambda n_u
+constexpr int kImpRegPlain = kFreeRegPlain;  // CUMF_IMPLICIT_REG_PLAIN (reg_u = lambda); else lambda n_u
 struct ImplicitArgs {
   // items of the materialising kernel / the short-row CG (the plan's lists); item_dst: system index of an item's row
   // (nullptr: row - row_begin)
@@ -68,7 +68,6 @@ inline long implicit_gram_slab(int f) {
 // The Gram partials of a table with 128 < f <= 512 (als_implicit_free.hip; launch_implicit_gram reduces them)
 hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* part, hipStream_t stream);
 // The matrix-free CG (als_implicit_free.hip): the arguments and segments of als_free.h, plus G and the confidence weights.
-constexpr int kFreeRows = 32;  // rows per workgroup of the row pass
 struct ImplicitFreeArgs : FreeArgs {
   const float* G;  // f x f Gram of `gather`
   float alpha;

@@ -26,6 +26,7 @@
 
 #include "als_device.h"
 #include "als_implicit.h"
+#include "als_loss.h"
 
 #ifndef CUMF_IMPLICIT_PART
 #define CUMF_IMPLICIT_PART 0
@@ -35,6 +36,7 @@ namespace cumf {
 
 // (no anonymous namespace: cumf_last_kernel_name reports the kernels as cumf::implicit_*; every name here is prefixed)
 constexpr int kImpThreads = 256;  // four waves
+static_assert(kImpThreads == kLossThreads, "the loss kernels run the workgroup sum of als_loss.h");
 constexpr int kImpStage = 32;     // gathered rows per LDS stage
 
 // LDS pitch of a stage of FP columns: the four rows one MFMA operand reads start 16 banks apart
@@ -451,19 +453,8 @@ __global__ __launch_bounds__(kImpThreads) void implicit_zero_rows_kernel(const i
 
 // ---- 4. the objective
 
-// fixed-order sum of the workgroup's values (thread 0 returns it)
-static __device__ double implicit_block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kImpThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // part[block] = sum over its rows' stored entries of (1 + w)(p - s)^2 - s^2 (+ lambda (|x_u|^2 + |y_i|^2) when the
-// regulariser is weighted: sum_u lambda n_u |x_u|^2 = sum over the stored entries of lambda |x_u|^2, the same for Y)
+// regulariser is weighted): the pass of als_loss.h, shared with the weighted objective (als_weighted.hip)
 __global__ __launch_bounds__(kImpThreads) void implicit_loss_sparse_kernel(const int* __restrict__ rowptr,
                                                                            const int* __restrict__ colidx,
                                                                            const float* __restrict__ val,
@@ -471,29 +462,12 @@ __global__ __launch_bounds__(kImpThreads) void implicit_loss_sparse_kernel(const
                                                                            const float* __restrict__ thetaT, long long m,
                                                                            int f, float lambda, float alpha, int reg_mode,
                                                                            double* __restrict__ part) {
-  __shared__ double red[kImpThreads];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double lam = lambda, alp = alpha;
-  double acc = 0.0;
-  for (long long u = (long long)blockIdx.x * 4 + wave; u < m; u += (long long)gridDim.x * 4) {
-    const float* x = XT + (size_t)u * f;
-    for (long long k = rowptr[u] + lane; k < rowptr[u + 1]; k += 64) {
-      const float* y = thetaT + (size_t)colidx[k] * f;
-      const double r = val[k];
-      double s = 0.0, xx = 0.0, yy = 0.0;
-      for (int c = 0; c < f; ++c) {
-        const double xc = x[c], yc = y[c];
-        s = fma(xc, yc, s);
-        xx = fma(xc, xc, xx);
-        yy = fma(yc, yc, yy);
-      }
-      const double w = alp * fabs(r), p = r > 0.0 ? 1.0 : 0.0;
-      acc += (1.0 + w) * (p - s) * (p - s) - s * s;
-      if (reg_mode != kImpRegPlain) acc += lam * (xx + yy);
-    }
-  }
-  const double t = implicit_block_sum(acc, red);
-  if (threadIdx.x == 0) part[blockIdx.x] = t;
+  const double alp = alpha;
+  loss_sparse_pass(rowptr, colidx, XT, thetaT, m, f, lambda, reg_mode != kImpRegPlain, part, [&](long long k, double s) {
+    const double r = val[k];
+    const double w = alp * fabs(r), p = r > 0.0 ? 1.0 : 0.0;
+    return (1.0 + w) * (p - s) * (p - s) - s * s;
+  });
 }
 
 // out = sum of the parts + <Gx, Gy>_F (+ lambda (tr Gx + tr Gy) when the regulariser is plain)
@@ -507,7 +481,7 @@ __global__ __launch_bounds__(kImpThreads) void implicit_loss_final_kernel(const 
   for (int e = threadIdx.x; e < f * f; e += kImpThreads) acc += Gx[e] * Gy[e];
   if (reg_mode == kImpRegPlain)
     for (int i = threadIdx.x; i < f; i += kImpThreads) acc += (double)lambda * (Gx[i * f + i] + Gy[i * f + i]);
-  const double t = implicit_block_sum(acc, red);
+  const double t = loss_block_sum(acc, red);
   if (threadIdx.x == 0) out[0] = t;
 }
 

@@ -4,9 +4,9 @@
 // The CG never forms A_u.  Each step needs, for every live row u, A_u v = G v + T_u^T (w o (T_u v)) + reg_u v (T_u the
 // row's gathered block of factor rows, w its confidence weights): the core of als_free_core.h with the weights and with G v.
 //   implicit_free_sparse_kernel  one wave per segment of a row (free_sparse_pass); b = sum_{r>0} (1 + w) y;
-//   implicit_free_row_kernel     kFreeRows rows per workgroup: their vectors staged in LDS, G v of all of them on
-//                                v_mfma_f32_16x16x4_f32 (G streamed from L2 once per block, never once per row), then one wave
-//                                per row (free_row_update).
+//   implicit_free_row_kernel     kFreeRows rows per workgroup (free_gram_rows): their vectors staged in LDS, G v of all of
+//                                them on v_mfma_f32_16x16x4_f32 (G streamed from L2 once per block, never once per row), then
+//                                one wave per row (free_row_update).
 // A row's result does not depend on which other rows share its workgroup or plan: the factors are bit-identical from run to
 // run and for any x_batch / theta_batch.
 #include <hip/hip_runtime.h>
@@ -86,65 +86,14 @@ hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* pa
 
 template <int Q>
 __global__ __launch_bounds__(kFreeThreads) void implicit_free_sparse_kernel(const ImplicitFreeArgs a, int first) {
-  free_sparse_pass<Q, true>(a, first, a.alpha);
+  free_sparse_pass<Q, kFreeWeightAlpha>(a, first, a.alpha);
 }
 
 // ---- the row pass: kFreeRows rows per workgroup.  mode 0 (after the first sparse pass): r = b - A x, p = r, rs = r.r;
 // mode 1: one CG step with A p.  last: the rows are done after this pass.
 template <int Q>
 __global__ __launch_bounds__(kFreeThreads) void implicit_free_row_kernel(const ImplicitFreeArgs a, int mode, int last) {
-  constexpr int P = 64 * Q + 4;  // LDS pitch: the 16 rows one MFMA operand reads start 4 banks apart
-  __shared__ float vs[kFreeRows * P];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int f = a.f, FT = (f + 15) / 16, FP = 16 * FT;
-  const long long r0 = (long long)blockIdx.x * kFreeRows;
-  const int nr = (int)(a.rows - r0 < kFreeRows ? a.rows - r0 : kFreeRows);
-  if (!__syncthreads_or((int)threadIdx.x < nr && !a.done[r0 + threadIdx.x])) return;  // every row of the block is done
-  const float* V = mode == 0 ? a.x : a.p;
-  for (int e = threadIdx.x; e < kFreeRows * FP; e += kFreeThreads) {
-    const int rr = e / FP, c = e - rr * FP;
-    vs[rr * P + c] = (rr < nr && c < f) ? V[(size_t)(r0 + rr) * f + c] : 0.f;
-  }
-  __syncthreads();
-  // G v of the block's rows: wave w takes the 16-column tiles J = w + 4 t of both 16-row tiles; v_mfma_f32_16x16x4_f32 with
-  // A[i][k] = v_i[k] (LDS) and B[k][j] = G[k][16 J + j] (G symmetric, read from L2)
-  f32x4 acc[Q][2];
-#pragma unroll
-  for (int t = 0; t < Q; ++t) acc[t][0] = acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kk = 0; kk < FP / 4; ++kk) {
-    const int k = 4 * kk + (lane >> 4);
-    const float a0 = vs[(lane & 15) * P + k], a1 = vs[(16 + (lane & 15)) * P + k];
-#pragma unroll
-    for (int t = 0; t < Q; ++t) {
-      const int J = wave + 4 * t;
-      if (J < FT) {  // uniform
-        const int c = 16 * J + (lane & 15);
-        const float g = (k < f && c < f) ? a.G[(size_t)k * f + c] : 0.f;
-        acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, g, acc[t][0], 0, 0, 0);
-        acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, g, acc[t][1], 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < Q; ++t) {
-    const int J = wave + 4 * t;
-    if (J < FT) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) vs[(16 * h + 4 * (lane >> 4) + r) * P + 16 * J + (lane & 15)] = acc[t][h][r];
-    }
-  }
-  __syncthreads();
-  for (int rr = wave; rr < nr; rr += 4) {
-    const long long row = r0 + rr;
-    if (a.done[row]) continue;  // uniform
-    const int n = a.row_len[row];
-    const float reg = a.reg_mode == kImpRegPlain ? a.lambda : (float)n * a.lambda;
-    free_row_update<Q, true>(a, row, n, reg, vs + rr * P, lane, mode, last);
-  }
+  free_gram_rows<Q, false>(a, 1.f, mode, last);
 }
 
 hipError_t launch_implicit_free_pass(const ImplicitFreeArgs& a, int step, int cg_iters, hipStream_t stream) {

@@ -1,5 +1,5 @@
 """ctypes loader of `cumf_als_amd/csrc/libALS.so` (the C ABI of include/cumf_als_capi.h, cumf_dist_capi.h,
-cumf_implicit_capi.h, cumf_topk_capi.h, cumf_nnls_capi.h, cumf_rank_capi.h, cumf_bias_capi.h and cumf_free_capi.h).
+cumf_implicit_capi.h, cumf_topk_capi.h, cumf_nnls_capi.h, cumf_rank_capi.h, cumf_bias_capi.h, cumf_free_capi.h and cumf_weighted_capi.h).
 
 The library is the product: there is no Python or CPU fallback.  `load()` raises
 when the shared object is missing or lacks a declared symbol.
@@ -131,12 +131,18 @@ FREE_ABI = {
     "cumf_matfree_available": (_i, [_i]),
     "cumf_als_update_matfree": (_i, [_vp, _ip, _fp, _fp, _fp, _f, _i, _vp]),
 }
+# include/cumf_weighted_capi.h (weighted ALS on the matrix-free core, als_weighted.cpp)
+WEIGHTED_ABI = {
+    "cumf_weighted_available": (_i, [_i]),
+    "cumf_als_update_weighted": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _vp]),
+    "cumf_weighted_loss": (_i, [_ip, _ip, _fp, _fp, _fp, _fp, _l, _l, _i, _f, _f, _i, _vp, _vp]),
+}
 ABI_BY_HEADER = {"cumf_als_capi.h": C_ABI, "cumf_dist_capi.h": DIST_ABI, "cumf_implicit_capi.h": IMPLICIT_ABI,
                  "cumf_topk_capi.h": TOPK_ABI, "cumf_nnls_capi.h": NNLS_ABI, "cumf_rank_capi.h": RANK_ABI,
-                 "cumf_bias_capi.h": BIAS_ABI, "cumf_free_capi.h": FREE_ABI}
+                 "cumf_bias_capi.h": BIAS_ABI, "cumf_free_capi.h": FREE_ABI, "cumf_weighted_capi.h": WEIGHTED_ABI}
 C_SYMBOLS, DIST_SYMBOLS, IMPLICIT_SYMBOLS = list(C_ABI), list(DIST_ABI), list(IMPLICIT_ABI)
 TOPK_SYMBOLS, NNLS_SYMBOLS, RANK_SYMBOLS = list(TOPK_ABI), list(NNLS_ABI), list(RANK_ABI)
-BIAS_SYMBOLS, FREE_SYMBOLS = list(BIAS_ABI), list(FREE_ABI)
+BIAS_SYMBOLS, FREE_SYMBOLS, WEIGHTED_SYMBOLS = list(BIAS_ABI), list(FREE_ABI), list(WEIGHTED_ABI)
 # C++-linkage drop-in symbols (include/als.h, include/cg.h) under the reference's mangled names
 CXX_SYMBOLS = [
     "_Z5doALSPKiS0_PKfS0_S0_S2_S0_PfS3_S0_S0_S2_iiillfiiii",
