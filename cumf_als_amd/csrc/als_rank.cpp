@@ -1,5 +1,5 @@
-// als_rank.cpp -- host side of full-ranking evaluation (include/cumf_rank_capi.h): argument checks, the slab cut (topk_cut, as
-// for top-k), scratch, launches.  Kernels: als_rank.hip.
+// als_rank.cpp -- host side of full-ranking evaluation (include/cumf_rank_capi.h): argument checks, the set-up shared with
+// top-k (score_setup, als_topk.cpp), scratch, launches.  Kernels: als_rank.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,47 +22,31 @@ extern "C" int cumf_heldout_ranks(const float* Q, long rows, const float* C, lon
                                   int excl_rowptr_is_64, const int* excl_colidx, const void* test_rowptr,
                                   int test_rowptr_is_64, const int* test_colidx, long n_test, int* ranks, int* n_eligible,
                                   void* stream) {
-  if (!rank_ok(f) || rows < 0 || ncand < 0 || ncand > 0x7fffffffL || n_test < 0 ||
-      (rows > 0 && (!Q || !n_eligible || !test_rowptr)) || (ncand > 0 && !C) || (n_test > 0 && (!test_colidx || !ranks)) ||
-      (!excl_rowptr) != (!excl_colidx)) {
+  RankArgs a{};
+  long long grid = 0;
+  int rc = (int)hipErrorInvalidValue;
+  if (n_test >= 0 && (rows <= 0 || (n_eligible && test_rowptr)) && (n_test <= 0 || (test_colidx && ranks)))
+    rc = score_setup(&a, Q, rows, C, ncand, f, excl_rowptr, excl_rowptr_is_64, excl_colidx, rank_count_occupancy, &grid);
+  if (rc == (int)hipErrorInvalidValue)
     fprintf(stderr,
             "cumf_heldout_ranks: needs 1 <= f <= %d (got %d), rows >= 0, 0 <= ncand < 2^31, n_test >= 0, the tables, the "
             "held-out CSR and the outputs, and both exclusion arrays or neither\n",
             kTopkMaxF, f);
-    return (int)hipErrorInvalidValue;
-  }
-  if (rows == 0) return 0;
+  if (rc || !grid) return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  int dev = 0, cus = 0;
-  CUMF_HIP_CHECK(hipGetDevice(&dev));
-  CUMF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const TopkCut cut = topk_cut(rows, ncand, std::max(cus, 1), rank_count_occupancy(f > kTopkJC));
   ScratchLease lease;
-  RankArgs a{};
-  a.Q = Q;
-  a.rows = rows;
-  a.C = C;
-  a.ncand = ncand;
-  a.f = f;
-  a.excl_rowptr = excl_rowptr;
-  a.rowptr64 = excl_rowptr_is_64 ? 1 : 0;
-  a.excl_colidx = excl_colidx;
-  a.vec = (f % 4 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
   a.test_rowptr = test_rowptr;
   a.test_rowptr64 = test_rowptr_is_64 ? 1 : 0;
   a.test_colidx = test_colidx;
   a.n_test = n_test;
-  a.nslab = cut.nslab;
-  a.slab_len = cut.slab_len;
-  a.n_items = cut.n_items;
   a.ranks = ranks;
   a.n_eligible = n_eligible;
-  int rc = scratch(s, kScratchRankKeys, (size_t)n_test, &a.keys);
+  rc = scratch(s, kScratchRankKeys, (size_t)n_test, &a.keys);
   if (!rc) rc = scratch(s, kScratchRankHist, (size_t)n_test, &a.hist);
   if (!rc) rc = scratch(s, kScratchRankValid, (size_t)rows, &a.nvalid);
   if (rc) return rc;
   CUMF_HIP_CHECK(launch_rank_thresholds(a, s));
-  CUMF_HIP_CHECK(launch_rank_count(a, cut.grid, s));
+  CUMF_HIP_CHECK(launch_rank_count(a, grid, s));
   if (n_test > 0) CUMF_HIP_CHECK(launch_rank_finish(a, s));
   return 0;
 }

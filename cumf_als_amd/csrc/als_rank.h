@@ -12,23 +12,11 @@ constexpr int kRankPoolW = 768;            // held-out keys (and buckets) a wave
 constexpr int kRankPool = 4 * kRankPoolW;  // ... per workgroup; a wave whose queries have more works on the global arrays
 constexpr int kRankMaxK = 16;              // cut-offs per cumf_rank_metrics call
 constexpr int kRankCols = 7;               // per-query metric columns in front of the 3 per cut-off
-struct RankArgs {
-  const float* Q;
-  long long rows;
-  const float* C;
-  long long ncand;
-  int f;
-  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
-  int rowptr64;
-  const int* excl_colidx;
-  int vec;                  // C rows may be read as float4 (f % 4 == 0, 16-byte aligned)
+struct RankArgs : ScoreArgs {
   const void* test_rowptr;  // rows + 1 entries, int32 or int64 (test_rowptr64)
   int test_rowptr64;
   const int* test_colidx;
   long long n_test;         // entries of test_colidx (and of keys, hist, ranks)
-  int nslab;
-  long long slab_len;       // candidates per slab, a multiple of kTopkNC
-  long long n_items;        // query blocks x slabs
   unsigned long long* keys; // per held-out entry: its key (0: not eligible), sorted in descending order within each row
   int* hist;                // per row: bucket b = eligible candidates below exactly b of the row's valid keys
   int* nvalid;              // per query: its non-zero keys

@@ -7,18 +7,18 @@
 //   rank_sort_kernel       one wave per query sorts the row's keys in place in descending order (a bitonic network whose
 //                          comparators all point the same way, so a row of any length needs no padding) and counts the
 //                          non-zero ones: the query's thresholds;
-//   rank_count_kernel      the hot path, shaped like topk_score_kernel: a workgroup owns kTopkQB queries (fragments in
-//                          registers) and one slab of the candidates, walked in blocks of kTopkNC staged in LDS.  A lane
-//                          drops a score that is NaN, excluded (forward-only cursor) or below its query's lowest threshold
-//                          (a register); every other score is located among the query's sorted thresholds by binary search,
+//   rank_count_kernel      the hot path, on the scoring core of als_score.h as topk_score_kernel is (score_item, the
+//                          exclusion cursor, score_block, score_row / score_eligible).  A lane counts its eligible scores
+//                          and drops those below its query's lowest threshold (a register); every other score is
+//                          located among the query's sorted thresholds by binary search,
 //                          b = thresholds with a larger key, and counted in the integer bucket hist[q][b].  A wave keeps the
 //                          thresholds and buckets of its kTopkQW queries in LDS when they fit kRankPoolW (the rows are
 //                          contiguous) and adds the buckets to the global ones at the end of the slab; a wave whose queries
-//                          have more searches and counts in the global arrays.  Eligible candidates are counted per lane;
+//                          have more searches and counts in the global arrays;
 //   rank_finish_kernel     one wave per query: rank of the j-th threshold = sum_{b <= j} hist[b] - 1 (the entry counted
 //                          itself), written at the entry's place in the held-out row;
 //   rank_metrics_kernel    one wave per query sorts the ranks of its relevant entries and reduces them to the per-query
-//                          values; rank_metrics_reduce_kernel sums those in query order in fp64.
+//                          values; rank_metrics_reduce_kernel sums those in query order in fp64 (score_column_sum).
 // Only integer atomics: every result is bit-identical from run to run and does not depend on the slab cut.
 #include <hip/hip_runtime.h>
 
@@ -52,12 +52,8 @@ __global__ __launch_bounds__(kTopkThreads) void rank_threshold_kernel(const Rank
   const int t = a.test_colidx[e];
   bool ok = t >= 0 && t < a.ncand;
   if (ok && a.excl_colidx) {
-    long long xl = topk_rowptr(a.excl_rowptr, a.rowptr64, q), xh = topk_rowptr(a.excl_rowptr, a.rowptr64, q + 1);
-    const long long xe = xh;
-    while (xl < xh) {
-      const long long mid = xl + ((xh - xl) >> 1);
-      if (a.excl_colidx[mid] < t) xl = mid + 1; else xh = mid;
-    }
+    const long long xe = topk_rowptr(a.excl_rowptr, a.rowptr64, q + 1);
+    const long long xl = score_lower_bound(a.excl_colidx, topk_rowptr(a.excl_rowptr, a.rowptr64, q), xe, t);
     ok = !(xl < xe && a.excl_colidx[xl] == t);
   }
   float s = 0.f;
@@ -105,15 +101,9 @@ __device__ __forceinline__ void rank_sort_row(topk_key* K, int n, int lane) {
   }
 }
 
-__device__ __forceinline__ int rank_wave_sum(int x) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
 __global__ __launch_bounds__(kTopkThreads) void rank_sort_kernel(const RankArgs a) {
   const int lane = threadIdx.x & 63;
-  const long long q = (long long)blockIdx.x * (kTopkThreads / 64) + (threadIdx.x >> 6);
+  const long long q = score_wave_query();
   if (q >= a.rows) return;
   long long tb, te;
   rank_row(a.test_rowptr, a.test_rowptr64, q, a.n_test, &tb, &te);
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_sort_kernel(const RankArgs 
   rank_sort_row(a.keys + tb, n, lane);
   int nv = 0;
   for (int i = lane; i < n; i += 64) nv += a.keys[tb + i] != 0ull;
-  nv = rank_wave_sum(nv);
+  nv = score_wave_sum(nv);
   if (lane == 0) a.nvalid[q] = nv;
 }
 
@@ -156,11 +146,9 @@ __global__ __launch_bounds__(kTopkThreads) void rank_count_kernel(const RankArgs
   int* whist = phist + wave * kRankPoolW;
   float qf[2][kTopkJC / 4];
   for (long long item = blockIdx.x; item < a.n_items; item += gridDim.x) {
-    const long long qb = item / a.nslab;
-    const int slab = (int)(item - qb * a.nslab);
-    const long long wq0 = qb * kTopkQB + kTopkQW * wave;  // first query of this wave
-    const long long cb = (long long)slab * a.slab_len;
-    const long long ce = cb + a.slab_len < a.ncand ? cb + a.slab_len : a.ncand;
+    long long wq0, cb, ce;  // first query of this wave; the slab's candidates
+    int slab;
+    score_item(a, item, wave, &wq0, &slab, &cb, &ce);
     // the wave's rows of held-out keys are contiguous: [w0, w1)
     long long w0 = 0, w1 = 0;
     if (wq0 < a.rows) {
@@ -176,7 +164,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_count_kernel(const RankArgs
       wpool[i] = a.keys[w0 + i];
       whist[i] = 0;
     }
-    // lanes 0..31: the wave's queries -- thresholds and the exclusion cursor (first entry >= cb)
+    // lanes 0..31: the wave's queries -- thresholds and the exclusion cursor
     const int qs = kTopkQW * wave + (lane & (kTopkQW - 1));  // query slot of lanes 0..31 (repeated above)
     const long long myq = wq0 + lane;
     long long xp = 0, xe = 0;
@@ -197,15 +185,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_count_kernel(const RankArgs
       tbase[qs] = (int)(tb - w0);
       tcnt[qs] = nv;
       tlow[qs] = nv > 0 ? topk_key_score(a.keys[tb + nv - 1]) : __builtin_nanf("");
-      if (a.excl_colidx && myq < a.rows) {
-        long long lo = topk_rowptr(a.excl_rowptr, a.rowptr64, myq), hi = topk_rowptr(a.excl_rowptr, a.rowptr64, myq + 1);
-        xe = hi;
-        while (lo < hi) {
-          const long long mid = lo + ((hi - lo) >> 1);
-          if (a.excl_colidx[mid] < cb) lo = mid + 1; else hi = mid;
-        }
-        xp = lo;
-      }
+      score_excl_begin(a, myq, cb, &xp, &xe);
     }
     topk_wave_sync();
     float thl[2][4];
@@ -220,72 +200,27 @@ __global__ __launch_bounds__(kTopkThreads) void rank_count_kernel(const RankArgs
     if (!MULTI) topk_load_query(qf, a, wq0, 0, a.f, lane);
     for (long long c0 = cb; c0 < ce; c0 += kTopkNC) {
       const int nc = (int)(ce - c0 < kTopkNC ? ce - c0 : kTopkNC);
-      if (lane < kTopkQW) {  // exclusion bits of [c0, c0 + nc): the cursor only moves forward
-        topk_key m = 0;
-        while (xp < xe) {
-          const int c = a.excl_colidx[xp];
-          if (c >= c0 + nc) break;
-          m |= 1ull << (c - c0);
-          ++xp;
-        }
-        xmask[qs] = m;
-      }
+      if (lane < kTopkQW) xmask[qs] = score_excl_mask(a, &xp, xe, c0, nc);
       f32x4 acc[2][4];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[qt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int j0 = 0; j0 < a.f; j0 += kTopkJC) {  // the MFMA sequence of topk_score_kernel
-        const int fc = a.f - j0 < kTopkJC ? a.f - j0 : kTopkJC;
-        const int nsteps = (fc + 3) >> 2;
-        __syncthreads();  // the previous chunk's readers are done with cs
-        topk_stage(cs, a.C, a.f, c0, nc, j0, fc, a.vec);
-        if (MULTI) topk_load_query(qf, a, wq0, j0, fc, lane);
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < kTopkJC / 16; ++b) {
-          if (4 * b < nsteps) {
-            float4 cv[4];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
-              cv[ct] = *reinterpret_cast<const float4*>(cs + (16 * ct + (lane & 15)) * kTopkPitch + 16 * b + 4 * (lane >> 4));
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              if (4 * b + t < nsteps) {
-                const float cvt[4] = {t == 0 ? cv[0].x : t == 1 ? cv[0].y : t == 2 ? cv[0].z : cv[0].w,
-                                      t == 0 ? cv[1].x : t == 1 ? cv[1].y : t == 2 ? cv[1].z : cv[1].w,
-                                      t == 0 ? cv[2].x : t == 1 ? cv[2].y : t == 2 ? cv[2].z : cv[2].w,
-                                      t == 0 ? cv[3].x : t == 1 ? cv[3].y : t == 2 ? cv[3].z : cv[3].w};
-#pragma unroll
-                for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                  for (int ct = 0; ct < 4; ++ct)
-                    acc[qt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[qt][4 * b + t], cvt[ct], acc[qt][ct], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-      // count: score (query 16 qt + 4 (lane >> 4) + r of the wave, candidate c0 + 16 ct + (lane & 15))
+      score_block<MULTI>(acc, qf, cs, a, wq0, c0, nc, lane);
+      // count: every eligible score, and those not below the query's lowest threshold among its thresholds
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int slot = kTopkQW * wave + 16 * qt + 4 * (lane >> 4) + r;
-          const bool qok = wq0 + 16 * qt + 4 * (lane >> 4) + r < a.rows;
-          const topk_key xm = xmask[slot];
+          const ScoreRow w = score_row(a, wq0, wave, xmask, lane, qt, r);
 #pragma unroll
           for (int ct = 0; ct < 4; ++ct) {
             const int cc = 16 * ct + (lane & 15);
             const float s = acc[qt][ct][r];
-            if (qok && cc < nc && s == s && !((xm >> cc) & 1ull)) {
+            if (score_eligible(w, cc, nc, s)) {
               ++nel[qt][r];
               if (s >= thl[qt][r]) {  // false without thresholds (NaN)
                 const topk_key key = topk_make_key(s, (int)(c0 + cc));
                 if (in_lds)
-                  rank_consume(wpool + tbase[slot], whist + tbase[slot], tcnt[slot], key);
+                  rank_consume(wpool + tbase[w.slot], whist + tbase[w.slot], tcnt[w.slot], key);
                 else
-                  rank_consume(a.keys + tglob[slot], a.hist + tglob[slot], tcnt[slot], key);
+                  rank_consume(a.keys + tglob[w.slot], a.hist + tglob[w.slot], tcnt[w.slot], key);
               }
             }
           }
@@ -315,7 +250,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_count_kernel(const RankArgs
 // One wave per query: ranks of its valid thresholds from the prefix sums of the buckets.
 __global__ __launch_bounds__(kTopkThreads) void rank_finish_kernel(const RankArgs a) {
   const int lane = threadIdx.x & 63;
-  const long long q = (long long)blockIdx.x * (kTopkThreads / 64) + (threadIdx.x >> 6);
+  const long long q = score_wave_query();
   if (q >= a.rows) return;
   long long tb, te;
   rank_row(a.test_rowptr, a.test_rowptr64, q, a.n_test, &tb, &te);
@@ -332,11 +267,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_finish_kernel(const RankArg
     }
     if (i < nv) {
       const int t = topk_key_id(a.keys[tb + i]);
-      long long lo = tb, hi = te;
-      while (lo < hi) {
-        const long long mid = lo + ((hi - lo) >> 1);
-        if (a.test_colidx[mid] < t) lo = mid + 1; else hi = mid;
-      }
+      const long long lo = score_lower_bound(a.test_colidx, tb, te, t);
       if (lo < te && a.test_colidx[lo] == t) a.ranks[lo] = before + x - 1;
     }
     before += __shfl(x, 63, 64);
@@ -344,12 +275,6 @@ __global__ __launch_bounds__(kTopkThreads) void rank_finish_kernel(const RankArg
 }
 
 // ---- metrics
-
-__device__ __forceinline__ double rank_wave_sum(double x) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
 
 // per query into part[q * (kRankCols + 3 n_k) ..]: (counted, auc counted, AUC, MPR numerator, MPR weight, MRR, AP), then
 // (precision, recall, NDCG) per cut-off
@@ -360,7 +285,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_metrics_kernel(const int* _
                                                                     const RankKs ks, topk_key* __restrict__ keys,
                                                                     double* __restrict__ part) {
   const int lane = threadIdx.x & 63;
-  const long long q = (long long)blockIdx.x * (kTopkThreads / 64) + (threadIdx.x >> 6);
+  const long long q = score_wave_query();
   if (q >= rows) return;
   long long tb, te;
   rank_row(rowptr, rowptr64, q, n_test, &tb, &te);
@@ -373,7 +298,7 @@ __global__ __launch_bounds__(kTopkThreads) void rank_metrics_kernel(const int* _
     keys[tb + i] = in ? ((topk_key)(0x80000000u - (unsigned)r) << 32) | (unsigned)i : 0ull;
     p += in;
   }
-  p = rank_wave_sum(p);
+  p = score_wave_sum(p);
   topk_wave_sync();
   rank_sort_row(keys + tb, n, lane);
   const double N = (double)n_eligible[q];
@@ -389,10 +314,10 @@ __global__ __launch_bounds__(kTopkThreads) void rank_metrics_kernel(const int* _
     }
     ap += (i + 1) / (r + 1.0);
   }
-  excess = rank_wave_sum(excess);
-  mprn = rank_wave_sum(mprn);
-  mprw = rank_wave_sum(mprw);
-  ap = rank_wave_sum(ap);
+  excess = score_wave_sum(excess);
+  mprn = score_wave_sum(mprn);
+  mprw = score_wave_sum(mprw);
+  ap = score_wave_sum(ap);
   const int W = kRankCols + 3 * ks.n;
   double* o = part + (size_t)q * W;
   const bool counted = p >= 1;
@@ -418,9 +343,9 @@ __global__ __launch_bounds__(kTopkThreads) void rank_metrics_kernel(const int* _
       }
       if (i < k) idcg += 1.0 / log2((double)(i + 2));
     }
-    hits = rank_wave_sum(hits);
-    dcg = rank_wave_sum(dcg);
-    idcg = rank_wave_sum(idcg);
+    hits = score_wave_sum(hits);
+    dcg = score_wave_sum(dcg);
+    idcg = score_wave_sum(idcg);
     if (lane == 0) {
       o[kRankCols + 3 * c] = counted ? hits / k : 0.0;
       o[kRankCols + 3 * c + 1] = counted ? hits / p : 0.0;
@@ -429,23 +354,15 @@ __global__ __launch_bounds__(kTopkThreads) void rank_metrics_kernel(const int* _
   }
 }
 
-// one workgroup: per column, thread t sums queries t, t + 256, ... in order, then a fixed tree (the scheme of
-// topk_metrics_reduce_kernel); out = (queries, auc queries, AUC, MPR, MRR, MAP), then (precision, recall, NDCG) per cut-off
+// one workgroup sums each column in query order (score_column_sum); out = (queries, auc queries, AUC, MPR, MRR, MAP), then (precision, recall, NDCG) per cut-off
 __global__ __launch_bounds__(kTopkThreads) void rank_metrics_reduce_kernel(const double* __restrict__ part, long long rows,
                                                                            int n_k, double* __restrict__ out) {
   __shared__ double red[kTopkThreads];
   __shared__ double tot[kRankCols + 3 * kRankMaxK];
   const int W = kRankCols + 3 * n_k;
   for (int c = 0; c < W; ++c) {
-    double s = 0.0;
-    for (long long q = threadIdx.x; q < rows; q += kTopkThreads) s += part[(size_t)q * W + c];
-    __syncthreads();  // the previous column's tree is read
-    red[threadIdx.x] = s;
-    for (int w = kTopkThreads / 2; w > 0; w >>= 1) {
-      __syncthreads();
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    }
-    if (threadIdx.x == 0) tot[c] = red[0];
+    const double s = score_column_sum(part, rows, W, c, red);
+    if (threadIdx.x == 0) tot[c] = s;
   }
   if (threadIdx.x == 0) {
     const double n = tot[0], na = tot[1];

@@ -1,5 +1,6 @@
-// als_topk.cpp -- host side of top-k recommendation and ranking metrics (include/cumf_topk_capi.h): argument checks, the slab
-// cut (topk_cut, als_topk.h), scratch, launches.  Kernels: als_topk.hip.
+// als_topk.cpp -- host side of top-k recommendation and ranking metrics (include/cumf_topk_capi.h): argument checks, scratch,
+// launches; and score_setup, the set-up every scoring launch shares (als_rank.cpp too): the slab cut (topk_cut, als_topk.h) and
+// the common arguments.  Kernels: als_topk.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,46 +17,59 @@ bool topk_ok(int f, int k) { return f >= 1 && f <= kTopkMaxF && k >= 1 && k <= k
 
 }  // namespace
 
+int cumf::score_setup(ScoreArgs* a, const float* Q, long long rows, const float* C, long long ncand, int f,
+                      const void* excl_rowptr, int rowptr_is_64, const int* excl_colidx, int (*occupancy)(bool multi),
+                      long long* grid) {
+  *grid = 0;
+  if (f < 1 || f > kTopkMaxF || rows < 0 || ncand < 0 || ncand > 0x7fffffffL || (rows > 0 && !Q) || (ncand > 0 && !C) ||
+      (!excl_rowptr) != (!excl_colidx))
+    return (int)hipErrorInvalidValue;
+  if (rows == 0) return 0;
+  int dev = 0, cus = 0;
+  CUMF_HIP_CHECK(hipGetDevice(&dev));
+  CUMF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const TopkCut cut = topk_cut(rows, ncand, std::max(cus, 1), occupancy(f > kTopkJC));
+  a->Q = Q;
+  a->rows = rows;
+  a->C = C;
+  a->ncand = ncand;
+  a->f = f;
+  a->excl_rowptr = excl_rowptr;
+  a->rowptr64 = rowptr_is_64 ? 1 : 0;
+  a->excl_colidx = excl_colidx;
+  a->vec = (f % 4 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
+  a->nslab = cut.nslab;
+  a->slab_len = cut.slab_len;
+  a->n_items = cut.n_items;
+  *grid = cut.grid;
+  return 0;
+}
+
 extern "C" int cumf_topk_available(int f, int k) { return topk_ok(f, k); }
 
 extern "C" int cumf_topk(const float* Q, long rows, const float* C, long ncand, int f, const void* excl_rowptr,
                          int rowptr_is_64, const int* excl_colidx, int k, int* ids, float* scores, void* stream) {
-  if (!topk_ok(f, k) || rows < 0 || ncand < 0 || ncand > 0x7fffffffL || (rows > 0 && (!Q || !ids || !scores)) ||
-      (ncand > 0 && !C) || (!excl_rowptr) != (!excl_colidx)) {
+  TopkArgs a{};
+  long long grid = 0;
+  int rc = (int)hipErrorInvalidValue;
+  if (topk_ok(f, k) && (rows <= 0 || (ids && scores)))
+    rc = score_setup(&a, Q, rows, C, ncand, f, excl_rowptr, rowptr_is_64, excl_colidx, topk_score_occupancy, &grid);
+  if (rc == (int)hipErrorInvalidValue)
     fprintf(stderr,
             "cumf_topk: needs 1 <= f <= %d (got %d), 1 <= k <= %d (got %d), rows >= 0, 0 <= ncand < 2^31, the tables and "
             "outputs, and both exclusion arrays or neither\n",
             kTopkMaxF, f, kTopkMaxK, k);
-    return (int)hipErrorInvalidValue;
-  }
-  if (rows == 0) return 0;
+  if (rc || !grid) return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  int dev = 0, cus = 0;
-  CUMF_HIP_CHECK(hipGetDevice(&dev));
-  CUMF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const TopkCut cut = topk_cut(rows, ncand, std::max(cus, 1), topk_score_occupancy(f > kTopkJC));
   ScratchLease lease;
-  TopkArgs a{};
-  a.Q = Q;
-  a.rows = rows;
-  a.C = C;
-  a.ncand = ncand;
-  a.f = f;
   a.k = k;
-  a.excl_rowptr = excl_rowptr;
-  a.rowptr64 = rowptr_is_64 ? 1 : 0;
-  a.excl_colidx = excl_colidx;
-  a.vec = (f % 4 == 0) && (reinterpret_cast<uintptr_t>(C) % 16 == 0);
-  a.nslab = cut.nslab;
-  a.slab_len = cut.slab_len;
-  a.n_items = cut.n_items;
   a.ids = ids;
   a.scores = scores;
-  int rc = scratch(s, kScratchTopkWork, (size_t)cut.grid * kTopkQB * (k + kTopkBuf), &a.work);
-  if (!rc && cut.nslab > 1) rc = scratch(s, kScratchTopkPart, (size_t)cut.nslab * rows * k, &a.part);
+  rc = scratch(s, kScratchTopkWork, (size_t)grid * kTopkQB * (k + kTopkBuf), &a.work);
+  if (!rc && a.nslab > 1) rc = scratch(s, kScratchTopkPart, (size_t)a.nslab * rows * k, &a.part);
   if (rc) return rc;
-  CUMF_HIP_CHECK(launch_topk_score(a, cut.grid, s));
-  if (cut.nslab > 1) CUMF_HIP_CHECK(launch_topk_merge(a.part, rows, k, cut.nslab, ids, scores, s));
+  CUMF_HIP_CHECK(launch_topk_score(a, grid, s));
+  if (a.nslab > 1) CUMF_HIP_CHECK(launch_topk_merge(a.part, rows, k, a.nslab, ids, scores, s));
   return 0;
 }
 

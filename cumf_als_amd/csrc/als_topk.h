@@ -19,19 +19,24 @@ constexpr int kTopkPitch = kTopkJC + 4;   // LDS row pitch: the 16 rows one k-gr
 constexpr int kTopkBuf = 128;             // survivor buffer per query (merged when above kTopkBuf - kTopkNC)
 constexpr int kTopkMaxK = 128;
 constexpr int kTopkMaxF = 512;
-struct TopkArgs {
+// What the scoring kernels share (als_score.h): the two tables, the exclusion CSR and the cut.  TopkArgs and RankArgs
+// (als_rank.h) extend it; score_setup fills it.
+struct ScoreArgs {
   const float* Q;
   long long rows;
   const float* C;
   long long ncand;
-  int f, k;
-  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
+  int f;
   int rowptr64;
+  const void* excl_rowptr;  // rows + 1 entries, int32 or int64 (rowptr64); null: no exclusion
   const int* excl_colidx;
   int vec;                  // C rows may be read as float4 (f % 4 == 0, 16-byte aligned)
   int nslab;
   long long slab_len;       // candidates per slab, a multiple of kTopkNC
   long long n_items;        // query blocks x slabs
+};
+struct TopkArgs : ScoreArgs {
+  int k;
   unsigned long long* work; // per workgroup: kTopkQB x (k + kTopkBuf) keys
   unsigned long long* part; // nslab > 1: nslab x rows x k keys
   int* ids;                 // nslab == 1: the result
@@ -68,6 +73,13 @@ inline TopkCut topk_cut(long long rows, long long ncand, int cus, int wgs_per_cu
   const long long items = qblocks * nslab;
   return TopkCut{(int)nslab, slab_len, items, std::min(items, slots)};
 }
+
+// The host set-up of a scoring launch, for cumf_topk and cumf_heldout_ranks alike: the argument checks they share
+// (hipErrorInvalidValue without a message: the caller's names its own function and limits), then the device's CU count, the
+// cut at `occupancy(f > kTopkJC)` workgroups per CU and the fields of *a.  rows == 0: returns 0 with *grid = 0 before any
+// device query.
+int score_setup(ScoreArgs* a, const float* Q, long long rows, const float* C, long long ncand, int f, const void* excl_rowptr,
+                int rowptr_is_64, const int* excl_colidx, int (*occupancy)(bool multi), long long* grid);
 
 }  // namespace cumf
 

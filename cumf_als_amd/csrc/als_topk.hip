@@ -3,15 +3,16 @@
 // The score of candidate c for query q is the fp32 fmaf chain s = fma(Q[q,j], C[c,j], s) over j = 0, 1, ..., f - 1 from +0;
 // v_mfma_f32_16x16x4_f32 issued in increasing j gives exactly those bits (f padded to a multiple of 4 with zeros).  Ranking is
 // the total order "higher score first, then lower index", encoded in one 64-bit key per (score, index): larger key = better.
-//   topk_score_kernel    a workgroup owns kTopkQB queries (kTopkQW per wave, their fragments in registers) and one slab of the
-//                        candidates, which it walks in blocks of kTopkNC staged in LDS.  Each lane filters its scores against
-//                        the query's current k-th score (a register), the exclusion bits of the block and NaN; survivors go
-//                        to a per-query buffer, which the owning wave merges into the query's sorted list (bitonic sort of
-//                        256 keys in registers) when it could overflow.  The grid is persistent: one list + buffer area per
-//                        workgroup in `work`.  One slab: the lists are the result; else they are the slab's partial lists;
+//   topk_score_kernel    on the scoring core of als_score.h: a workgroup owns kTopkQB queries and one slab of the candidates,
+//                        which it walks in blocks of kTopkNC (score_item, the exclusion cursor, score_block).  Each lane
+//                        filters its eligible scores (score_row, score_eligible) against the query's current k-th score (a
+//                        register); survivors go to a per-query buffer, which the owning wave merges into the query's sorted
+//                        list (bitonic sort of 256 keys in registers) when it could overflow.  The grid is persistent: one
+//                        list + buffer area per workgroup in `work`.  One slab: the lists are the result; else they are
+//                        the slab's partial lists;
 //   topk_merge_kernel    one wave per query merges the partial lists of the slabs in slab order;
 //   topk_metrics_kernel  one wave per query: hits by binary search in the sorted held-out row, then precision / recall / NDCG;
-//                        topk_metrics_reduce_kernel sums the per-query values in query order in fp64.
+//                        topk_metrics_reduce_kernel sums the per-query values in query order in fp64 (score_column_sum).
 // Every result is bit-identical from run to run: no float atomics, and the result of a query does not depend on the slab cut.
 #include <hip/hip_runtime.h>
 
@@ -22,7 +23,6 @@
 namespace cumf {
 
 // (no anonymous namespace: cumf_last_kernel_name reports the kernels as cumf::topk_*)
-// the key of the total order, topk_wave_sync, topk_rowptr, topk_stage and topk_load_query: als_score.h
 
 __device__ __forceinline__ topk_key topk_shfl_xor(topk_key v, int d) {
   const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, d, 64);
@@ -114,28 +114,17 @@ __global__ __launch_bounds__(kTopkThreads) void topk_score_kernel(const TopkArgs
   topk_key* buf = list + (size_t)kTopkQB * k;
   float qf[2][kTopkJC / 4];
   for (long long item = blockIdx.x; item < a.n_items; item += gridDim.x) {
-    const long long qb = item / a.nslab;
-    const int slab = (int)(item - qb * a.nslab);
-    const long long wq0 = qb * kTopkQB + kTopkQW * wave;  // first query of this wave
-    const long long cb = (long long)slab * a.slab_len;
-    const long long ce = cb + a.slab_len < a.ncand ? cb + a.slab_len : a.ncand;
-    // lanes 0..31: the wave's queries -- list state and the exclusion cursor (first entry >= cb)
+    long long wq0, cb, ce;  // first query of this wave; the slab's candidates
+    int slab;
+    score_item(a, item, wave, &wq0, &slab, &cb, &ce);
+    // lanes 0..31: the wave's queries -- list state and the exclusion cursor
     const int qs = kTopkQW * wave + (lane & (kTopkQW - 1));  // query slot of lanes 0..31 (repeated above)
-    const long long myq = wq0 + lane;
     long long xp = 0, xe = 0;
     if (lane < kTopkQW) {
       cnt[qs] = 0;
       nlist[qs] = 0;
       thr[qs] = kTopkOpen;
-      if (a.excl_colidx && myq < a.rows) {
-        long long lo = topk_rowptr(a.excl_rowptr, a.rowptr64, myq), hi = topk_rowptr(a.excl_rowptr, a.rowptr64, myq + 1);
-        xe = hi;
-        while (lo < hi) {
-          const long long mid = lo + ((hi - lo) >> 1);
-          if (a.excl_colidx[mid] < cb) lo = mid + 1; else hi = mid;
-        }
-        xp = lo;
-      }
+      score_excl_begin(a, wq0 + lane, cb, &xp, &xe);
     }
     topk_wave_sync();
     float th[2][4];
@@ -146,68 +135,22 @@ __global__ __launch_bounds__(kTopkThreads) void topk_score_kernel(const TopkArgs
     if (!MULTI) topk_load_query(qf, a, wq0, 0, a.f, lane);
     for (long long c0 = cb; c0 < ce; c0 += kTopkNC) {
       const int nc = (int)(ce - c0 < kTopkNC ? ce - c0 : kTopkNC);
-      if (lane < kTopkQW) {  // exclusion bits of [c0, c0 + nc): the cursor only moves forward
-        topk_key m = 0;
-        while (xp < xe) {
-          const int c = a.excl_colidx[xp];
-          if (c >= c0 + nc) break;
-          m |= 1ull << (c - c0);
-          ++xp;
-        }
-        xmask[qs] = m;
-      }
+      if (lane < kTopkQW) xmask[qs] = score_excl_mask(a, &xp, xe, c0, nc);
       f32x4 acc[2][4];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[qt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int j0 = 0; j0 < a.f; j0 += kTopkJC) {
-        const int fc = a.f - j0 < kTopkJC ? a.f - j0 : kTopkJC;
-        const int nsteps = (fc + 3) >> 2;
-        __syncthreads();  // the previous chunk's readers are done with cs
-        topk_stage(cs, a.C, a.f, c0, nc, j0, fc, a.vec);
-        if (MULTI) topk_load_query(qf, a, wq0, j0, fc, lane);
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < kTopkJC / 16; ++b) {
-          if (4 * b < nsteps) {
-            float4 cv[4];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
-              cv[ct] = *reinterpret_cast<const float4*>(cs + (16 * ct + (lane & 15)) * kTopkPitch + 16 * b + 4 * (lane >> 4));
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              if (4 * b + t < nsteps) {
-                const float cvt[4] = {t == 0 ? cv[0].x : t == 1 ? cv[0].y : t == 2 ? cv[0].z : cv[0].w,
-                                      t == 0 ? cv[1].x : t == 1 ? cv[1].y : t == 2 ? cv[1].z : cv[1].w,
-                                      t == 0 ? cv[2].x : t == 1 ? cv[2].y : t == 2 ? cv[2].z : cv[2].w,
-                                      t == 0 ? cv[3].x : t == 1 ? cv[3].y : t == 2 ? cv[3].z : cv[3].w};
-#pragma unroll
-                for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                  for (int ct = 0; ct < 4; ++ct)
-                    acc[qt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[qt][4 * b + t], cvt[ct], acc[qt][ct], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-      // filter: score (query 16 qt + 4 (lane >> 4) + r of the wave, candidate c0 + 16 ct + (lane & 15))
+      score_block<MULTI>(acc, qf, cs, a, wq0, c0, nc, lane);
+      // filter: above the query's k-th score so far -> its buffer
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int ql = 16 * qt + 4 * (lane >> 4) + r;
-          const bool qok = wq0 + ql < a.rows;
-          const topk_key xm = xmask[kTopkQW * wave + ql];
+          const ScoreRow w = score_row(a, wq0, wave, xmask, lane, qt, r);
 #pragma unroll
           for (int ct = 0; ct < 4; ++ct) {
             const int cc = 16 * ct + (lane & 15);
             const float s = acc[qt][ct][r];
-            // !(s <= th): s > th, or th open (NaN); s == s: not NaN
-            if (qok && cc < nc && s == s && !(s <= th[qt][r]) && !((xm >> cc) & 1ull)) {
-              const int slot = atomicAdd(&cnt[kTopkQW * wave + ql], 1);
-              buf[(size_t)(kTopkQW * wave + ql) * kTopkBuf + slot] = topk_make_key(s, (int)(c0 + cc));
+            if (score_eligible(w, cc, nc, s) && !(s <= th[qt][r])) {  // s > th, or th open (NaN)
+              const int at = atomicAdd(&cnt[w.slot], 1);
+              buf[(size_t)w.slot * kTopkBuf + at] = topk_make_key(s, (int)(c0 + cc));
             }
           }
         }
@@ -257,7 +200,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_score_kernel(const TopkArgs
 __global__ __launch_bounds__(kTopkThreads) void topk_merge_kernel(const topk_key* __restrict__ part, long long rows, int k,
                                                                   int nslab, int* __restrict__ ids, float* __restrict__ scores) {
   const int lane = threadIdx.x & 63;
-  const long long q = (long long)blockIdx.x * (kTopkThreads / 64) + (threadIdx.x >> 6);
+  const long long q = score_wave_query();
   if (q >= rows) return;
   topk_key v[4] = {0ull, 0ull, 0ull, 0ull};
   for (int s = 0; s < nslab; ++s) {
@@ -281,12 +224,6 @@ __global__ __launch_bounds__(kTopkThreads) void topk_merge_kernel(const topk_key
 
 // ---- ranking metrics
 
-__device__ __forceinline__ double topk_wave_sum(double x) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
 // per query: (counted, precision, recall, ndcg) into part[4 q ..]; a query without relevant held-out entries counts 0
 __global__ __launch_bounds__(kTopkThreads) void topk_metrics_kernel(const int* __restrict__ ids, long long rows, int k,
                                                                     const void* rowptr, int rowptr64,
@@ -294,31 +231,27 @@ __global__ __launch_bounds__(kTopkThreads) void topk_metrics_kernel(const int* _
                                                                     const float* __restrict__ val,
                                                                     double* __restrict__ part) {
   const int lane = threadIdx.x & 63;
-  const long long q = (long long)blockIdx.x * (kTopkThreads / 64) + (threadIdx.x >> 6);
+  const long long q = score_wave_query();
   if (q >= rows) return;
   const long long tb = topk_rowptr(rowptr, rowptr64, q), te = topk_rowptr(rowptr, rowptr64, q + 1);
   double nrel = 0.0;
   for (long long p = tb + lane; p < te; p += 64) nrel += (!val || val[p] > 0.f) ? 1.0 : 0.0;
-  nrel = topk_wave_sum(nrel);
+  nrel = score_wave_sum(nrel);
   double hits = 0.0, dcg = 0.0, idcg = 0.0;
   for (int j = lane; j < k; j += 64) {
     const double gain = 1.0 / log2((double)(j + 2));
     if (j < nrel) idcg += gain;
     const int id = ids[(size_t)q * k + j];
     if (id < 0) continue;
-    long long lo = tb, hi = te;
-    while (lo < hi) {
-      const long long mid = lo + ((hi - lo) >> 1);
-      if (colidx[mid] < id) lo = mid + 1; else hi = mid;
-    }
+    const long long lo = score_lower_bound(colidx, tb, te, id);
     if (lo < te && colidx[lo] == id && (!val || val[lo] > 0.f)) {
       hits += 1.0;
       dcg += gain;
     }
   }
-  hits = topk_wave_sum(hits);
-  dcg = topk_wave_sum(dcg);
-  idcg = topk_wave_sum(idcg);
+  hits = score_wave_sum(hits);
+  dcg = score_wave_sum(dcg);
+  idcg = score_wave_sum(idcg);
   if (lane == 0) {
     double* o = part + 4 * q;
     const bool counted = nrel >= 1.0;
@@ -329,26 +262,16 @@ __global__ __launch_bounds__(kTopkThreads) void topk_metrics_kernel(const int* _
   }
 }
 
-// one workgroup: thread t sums queries t, t + 256, ... in order, then a fixed tree; out = (count, means)
+// one workgroup sums the four columns in query order (score_column_sum); out = (count, means)
 __global__ __launch_bounds__(kTopkThreads) void topk_metrics_reduce_kernel(const double* __restrict__ part, long long rows,
                                                                            double* __restrict__ out) {
-  __shared__ double red[4][kTopkThreads];
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (long long q = threadIdx.x; q < rows; q += kTopkThreads)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s[c] += part[4 * q + c];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = s[c];
-  for (int w = kTopkThreads / 2; w > 0; w >>= 1) {
-    __syncthreads();
-    if ((int)threadIdx.x < w)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + w];
-  }
+  __shared__ double red[kTopkThreads];
+  double tot[4];
+  for (int c = 0; c < 4; ++c) tot[c] = score_column_sum(part, rows, 4, c, red);
   if (threadIdx.x == 0) {
-    const double n = red[0][0];
+    const double n = tot[0];
     out[0] = n;
-    for (int c = 1; c < 4; ++c) out[c] = n > 0.0 ? red[c][0] / n : 0.0;
+    for (int c = 1; c < 4; ++c) out[c] = n > 0.0 ? tot[c] / n : 0.0;
   }
 }
 
