@@ -33,6 +33,19 @@ def systems(rowptr, colidx, val, Y, lam, alpha, reg="weighted", dtype=np.float64
     return A, b
 
 
+def rhs_scale(rowptr, colidx, val, Y, alpha):
+    """The |b| formula (rows x f, fp64): sum (1 + w) |y| over the positive entries of every row, the scale of the rounding
+    error of b."""
+    rows = len(rowptr) - 1
+    Ya = np.abs(np.asarray(Y, np.float64))
+    cabs = np.zeros((rows, Ya.shape[1]), np.float64)
+    for u in range(rows):
+        s, e = int(rowptr[u]), int(rowptr[u + 1])
+        c = np.where(val[s:e] > 0, 1 + alpha * np.abs(val[s:e]), 0).astype(np.float64)
+        cabs[u] = c @ Ya[colidx[s:e]] if e > s else 0
+    return cabs
+
+
 def dense_loss(R_stored, X, Y, lam, alpha, reg="weighted"):
     """The objective by brute force over ALL entries: R_stored is an m x n array with NaN where nothing is stored."""
     X, Y = np.asarray(X, np.float64), np.asarray(Y, np.float64)
@@ -48,9 +61,14 @@ def dense_loss(R_stored, X, Y, lam, alpha, reg="weighted"):
     return L + float((ru * (X ** 2).sum(1)).sum() + (ri * (Y ** 2).sum(1)).sum())
 
 
-def sparse_loss(rowptr, colidx, val, X, Y, lam, alpha, reg="weighted"):
-    """<X^T X, Y^T Y>_F + sum_stored [(1 + w)(p - s)^2 - s^2] + regs, fp64 (what cumf_implicit_loss evaluates)."""
+def sparse_loss(rowptr, colidx, val, X, Y, lam, alpha, reg="weighted", absolute=False):
+    """<X^T X, Y^T Y>_F + sum_stored [(1 + w)(p - s)^2 - s^2] + regs, fp64 (what cumf_implicit_loss evaluates).  absolute:
+    the same sum with every term replaced by its absolute value, on |X| and |Y|: <|X|^T |X|, |Y|^T |Y|>_F + sum_stored
+    [(1 + w)(p + s)^2 + s^2] + regs with s = |x_u| . |y_i| (the scale of the rounding error of an evaluation, where the
+    - s^2 terms may cancel the rest)."""
     X, Y = np.asarray(X, np.float64), np.asarray(Y, np.float64)
+    if absolute:
+        X, Y = np.abs(X), np.abs(Y)
     rowptr = np.asarray(rowptr, np.int64)
     L = float(((X.T @ X) * (Y.T @ Y)).sum())
     row = np.repeat(np.arange(len(rowptr) - 1), np.diff(rowptr))
@@ -59,7 +77,7 @@ def sparse_loss(rowptr, colidx, val, X, Y, lam, alpha, reg="weighted"):
     s = np.einsum("ij,ij->i", X[row], Y[col])
     w = alpha * np.abs(r)
     p = (r > 0).astype(np.float64)
-    L += float(((1 + w) * (p - s) ** 2 - s ** 2).sum())
+    L += float(((1 + w) * (p + s) ** 2 + s ** 2).sum() if absolute else ((1 + w) * (p - s) ** 2 - s ** 2).sum())
     xx, yy = (X ** 2).sum(1), (Y ** 2).sum(1)
     if reg == "weighted":
         L += lam * float(xx[row].sum() + yy[col].sum())

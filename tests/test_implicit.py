@@ -69,3 +69,30 @@ def test_reference_sparse_loss_equals_the_dense_sum(reg):
         dense = ref.dense_loss(R, X, Y, 0.2, alpha, reg)
         sparse = ref.sparse_loss(rowptr, colidx, val, X, Y, 0.2, alpha, reg)
         assert abs(dense - sparse) <= 1e-10 * abs(dense), (dense, sparse)
+
+
+@pytest.mark.parametrize("reg", ["weighted", "plain"])
+def test_reference_sparse_loss_absolute_is_the_sum_of_absolute_terms(reg):
+    """sparse_loss(absolute=True) against the brute-force sum over ALL entries of |x_u| . |y_i| squared plus the stored
+    entries' (1 + w)(p + s)^2 + s^2 and the regularisers; it does not see the signs of the factors, bounds |L|, and the
+    |b| scale of the systems is their absolute right-hand side."""
+    R, rowptr, colidx, val, X, Y = _tiny(5)
+    lam = 0.2
+    stored = ~np.isnan(R)
+    S = np.abs(X) @ np.abs(Y).T
+    nu, ni = stored.sum(1), stored.sum(0)
+    ru, ri = (lam * nu, lam * ni) if reg == "weighted" else (np.full(len(nu), lam), np.full(len(ni), lam))
+    regs = float((ru * (X ** 2).sum(1)).sum() + (ri * (Y ** 2).sum(1)).sum())
+    flip = np.random.RandomState(1).choice([-1.0, 1.0], X.shape)
+    for alpha in (1.0, 40.0):
+        Rv = np.where(stored, R, 0.0)
+        w = np.where(stored, alpha * np.abs(Rv), 0.0)
+        p = (stored & (Rv > 0)).astype(np.float64)
+        want = float((S ** 2).sum() + (stored * ((1 + w) * (p + S) ** 2 + S ** 2)).sum()) + regs
+        got = ref.sparse_loss(rowptr, colidx, val, X, Y, lam, alpha, reg, absolute=True)
+        assert abs(got - want) <= 1e-12 * want, (got, want)
+        assert got == ref.sparse_loss(rowptr, colidx, val, X * flip, -Y, lam, alpha, reg, absolute=True)
+        assert abs(ref.sparse_loss(rowptr, colidx, val, X, Y, lam, alpha, reg)) <= got
+        assert abs(ref.sparse_loss(rowptr, colidx, val, X * flip, -Y, lam, alpha, reg)) <= got
+        _, babs = ref.systems(rowptr, colidx, val, Y, lam, alpha, reg, absolute=True)
+        assert np.array_equal(ref.rhs_scale(rowptr, colidx, val, Y, alpha), babs)

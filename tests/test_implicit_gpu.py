@@ -65,11 +65,7 @@ def test_get_hermitian_implicit(alslib, f):
             Aabs, babs = ref.systems(rowptr, colidx, val, Y, 0.05, alpha, reg, absolute=True)
             t, r = tt.cpu().numpy(), rhs.cpu().numpy()
             assert (np.abs(t - A64) <= 1e-5 * Aabs).all(), (f, alpha, reg, np.abs(t - A64).max())
-            cabs = np.zeros_like(babs)  # |b| formula: sum (1 + w) |y| over the positive entries
-            for u in range(len(lens)):
-                s, e = rowptr[u], rowptr[u + 1]
-                c = np.where(val[s:e] > 0, 1 + alpha * np.abs(val[s:e]), 0).astype(np.float64)
-                cabs[u] = c @ np.abs(Y[colidx[s:e]].astype(np.float64)) if e > s else 0
+            cabs = ref.rhs_scale(rowptr, colidx, val, Y, alpha)  # |b| formula: sum (1 + w) |y| over the positive entries
             assert (np.abs(r - b64) <= 1e-5 * cabs + 1e-30).all(), (f, alpha, reg, np.abs(r - b64).max())
             assert torch.equal(tt, tt2) and torch.equal(rhs, rhs2)
 
