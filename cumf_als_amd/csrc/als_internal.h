@@ -157,7 +157,7 @@ enum { kArithSplit3 = 0, kArithFast = 1, kArithPre = 2, kArithPrePk = 3, kArithS
 // ---- Routing of a half-iteration (als_route.cpp): which kernels, arithmetic and solvers a call runs on.
 // Every run-time knob that routes, read in one place.  gram / presplit: the environment (CUMF_ALS_GRAM,
 // CUMF_ALS_PRESPLIT) on first use, then what cumf_set_gram_mode / cumf_set_presplit set; presplit_mb, splitpk,
-// short_cg: the environment once per process; dual, batched, wave_solve, lu_exact: the environment on every call.
+// short_cg: the environment once per process; dual, lu16, batched, wave_solve, lu_exact: the environment on every call.
 struct Switches {
   int gram;            // kGram*                       CUMF_ALS_GRAM = exact | fast | (split)
   int presplit;        // CUMF_PRESPLIT_*              CUMF_ALS_PRESPLIT = 0 | 1 | 2
@@ -165,6 +165,7 @@ struct Switches {
   bool splitpk;        // kArithSplitPk wanted         CUMF_ALS_SPLITPK=0 turns it off
   bool short_cg;       // Gram-free CG of short rows   CUMF_ALS_SHORT_CG=0 turns it off
   bool dual;           // dual-form LU of short rows   CUMF_ALS_DUAL=0 turns it off
+  bool lu16;           // 16-pivot steps, one-wave LU  CUMF_ALS_LU16=0: the four-pivot panels
   bool batched;        // two-wave path (f >= 112)     CUMF_ALS_NO_BATCHED turns it off
   bool wave_solve;     // wave CG of chunked rows      CUMF_ALS_NO_WAVE_SOLVE turns it off
   bool lu_exact;       // oracle-order batched LU      CUMF_ALS_LU_EXACT=1
@@ -210,7 +211,13 @@ struct Route {
   // LU on one wave, pre-split table: the n_dual whole rows in front of the last n_dual_behind (rows without ratings: they
   // stay on the wave kernel) go to the dual-form kernel (als_dual.hip)
   long n_dual, n_dual_behind;
+  bool lu16;  // one-wave LU: sixteen pivots per step (where lu16_default(NB)), else the four-pivot panels
 };
+// feature-block counts whose one-wave LU eliminates sixteen pivots per step by default: where it was measured faster
+// (profiles/lu16/: NB = 7 Theta side 9.1 -> 8.7 ms; NB = 5 was 5.4 -> 5.7 ms at f = 64 -- one diagonal tile per three tiles of
+// block row instead of one per four -- and keeps the four-pivot panels, as does the dual kernel's lu_wave_blocked<5>:
+// 0.923 -> 0.934 ms)
+constexpr bool lu16_default(int nb) { return nb == 7; }
 Route route_for(int f, int mode, const PlanFacts& plan, const Switches& sw);
 hipError_t launch_half_iteration(const KernelArgs& a, int mode, const Route& r, const PlanLists& lists, hipStream_t stream);
 

@@ -213,6 +213,54 @@ __device__ __forceinline__ void lu_prep_step_s(const ACC& acc, LuPrepS<NB>& s, f
   }
 }
 
+// value of lane K of every row of 16 lanes in all 16 (DPP row_newbcast)
+template <int K>
+__device__ __forceinline__ float row_bcast(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + K, 0xf, 0xf, true));
+}
+// One pivot step of the 16-pivot elimination of a diagonal tile held as M[i = c][j = 4 g + r] with the rows of E = L^-1
+// beside it: row i += m_i (row K) on the eight registers, row K by row_newbcast folded into the v_fmac (one s_nop pair for the
+// DPP read of m's neighbours' registers behind their VALU writes).
+// Only the registers that some lane group still needs: column 4 g + r of M is live for 4 g + r > K (r > K - 12 at g = 3), column
+// 4 g + r of row K of E is non-zero for 4 g + r <= K (r <= K at g = 0).
+// ONE asm block per step: no register is written and then read through DPP inside it, and the s_nop pair at its head covers
+// the two wait states a DPP read needs behind any VALU write in front of the block (inline asm is opaque to the hazard
+// recogniser).  The register the next step's ds_bpermute reads goes first.
+template <int K>
+__device__ __forceinline__ void lu16_row_step(float (&n)[4], float (&e)[4], float m) {
+  static_assert(K >= 0 && K < 15, "the last pivot eliminates nothing");
+  constexpr int NN = K < 12 ? 4 : 15 - K, NE = K < 3 ? K + 1 : 4, NR = NN + NE;
+  float* p[8];
+  int cnt = 0;
+  p[cnt++] = &n[(K + 1) & 3];
+  static_for<4>([&](auto rc) {
+    constexpr int r = decltype(rc)::value;
+    if constexpr (r > K - 12 && r != ((K + 1) & 3)) p[cnt++] = &n[r];
+  });
+  static_for<4>([&](auto rc) {
+    constexpr int r = decltype(rc)::value;
+    if constexpr (r <= K) p[cnt++] = &e[r];
+  });
+#define CUMF_LU16_F(i) "v_fmac_f32_dpp %" #i ", %" #i ", %[m] row_newbcast:%[k] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define CUMF_LU16_5 CUMF_LU16_F(0) CUMF_LU16_F(1) CUMF_LU16_F(2) CUMF_LU16_F(3) CUMF_LU16_F(4)
+  if constexpr (NR == 5)
+    asm("s_nop 1\n\t" CUMF_LU16_5 : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]) : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 6)
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5)
+        : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]), "+v"(*p[5])
+        : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 7)
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6)
+        : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]), "+v"(*p[5]), "+v"(*p[6])
+        : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 8)
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6) CUMF_LU16_F(7)
+        : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]), "+v"(*p[5]), "+v"(*p[6]), "+v"(*p[7])
+        : [m] "v"(m), [k] "n"(K));
+#undef CUMF_LU16_5
+#undef CUMF_LU16_F
+}
+
 // exact three-way split of (a, b) into packed bf16 pairs (a in the low half), as split_micro does for the gathered rows
 __device__ __forceinline__ void split3_pair(float a, float b, unsigned& H, unsigned& M, unsigned& Lw) {
   H = pack_bf16(a, b);

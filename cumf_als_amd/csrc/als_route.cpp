@@ -30,6 +30,7 @@ Switches switches() {
   static const bool splitpk = !(getenv("CUMF_ALS_SPLITPK") && *getenv("CUMF_ALS_SPLITPK") == '0');
   static const bool short_cg = !getenv("CUMF_ALS_SHORT_CG") || atoi(getenv("CUMF_ALS_SHORT_CG")) != 0;
   const char* dual = getenv("CUMF_ALS_DUAL");
+  const char* lu16 = getenv("CUMF_ALS_LU16");
   const char* lu_exact = getenv("CUMF_ALS_LU_EXACT");
   return Switches{g_gram_mode,
                   g_presplit_mode,
@@ -37,6 +38,7 @@ Switches switches() {
                   splitpk,
                   short_cg,
                   !dual || atoi(dual) != 0,
+                  !lu16 || atoi(lu16) != 0,
                   !getenv("CUMF_ALS_NO_BATCHED"),
                   !getenv("CUMF_ALS_NO_WAVE_SOLVE"),
                   lu_exact && atoi(lu_exact) != 0};
@@ -78,6 +80,8 @@ static bool presplit_wanted(int f, long gather_rows, const Switches& sw) {
 //   dual rows  LU plans on one wave in the production pre-split form (kArithPrePk, f = 96 .. 111): the whole rows of
 //          1 .. kDualMaxRow ratings (the plan lists them last in every item list) solve their n x n dual system
 //          (als_dual.hip).  Rows without ratings stay (the reference's NaN).  CUMF_ALS_DUAL=0: none.
+//   lu16   the one-wave LU of NB = 7 eliminates sixteen pivots per step (lu_wave_blocked16); CUMF_ALS_LU16=0: the four-pivot
+//          panels (the _p4 instances), which NB < 7 and the dual kernel keep (measured slower there: profiles/lu16/).
 //   sse    every solver but two adds the train SSE of its rows: the workgroup CG of als_reduce_kernel, and its thread-grid LU
 //          below NB = 7 -- the chunked rows of LU plans below f = 96 and of CG plans at f = 112 .. 128 are not covered.
 Route route_for(int f, int mode, const PlanFacts& p, const Switches& sw) {
@@ -120,6 +124,7 @@ Route route_for(int f, int mode, const PlanFacts& p, const Switches& sw) {
                     dual_rows_available(f);
   r.n_dual = dual ? p.n_dual : 0;
   r.n_dual_behind = r.n_dual > 0 ? p.n_empty : 0;
+  r.lu16 = one && mode == kModeLU && sw.lu16 && lu16_default(nb);
   r.sse = wave && mode != kModeMaterialize &&
           (p.n_mrows == 0 || r.chunked == kSolveWaveCG || (mode == kModeLU && nb >= 7));
   return r;

@@ -101,8 +101,10 @@ __device__ __forceinline__ void fast_unscale(f32x4 (&acc)[(NB * (NB + 1) / 2 + N
 // five of them in scratch (41 spilled registers, 2.9 GB of scratch writes per Netflix Theta launch; 0 without it).
 // (the CG instances of the small systems sit at the edge of three waves per SIMD -- 166 registers at NB = 5 -- and the packed form
 // went over it: 174 registers, Theta side 4.6 -> 4.95 ms at f = 64; held at three)
-template <int NB, int MODE, int FC, int ARITH = kArithSplit3, bool WHOLE = false>
-__global__ __launch_bounds__(64, (NB <= 5 && MODE == kModeCG) ? 3 : CUMF_WAVE_MIN_WAVES) void als_wave_kernel(const KernelArgs a) {
+// P16: the LU eliminates sixteen pivots per step (lu_wave_blocked16) -- als_wave_kernel where lu16_default(NB) -- or four
+// (als_wave_kernel_p4: the instances CUMF_ALS_LU16=0 routes to).
+template <int NB, int MODE, int FC, int ARITH, bool WHOLE, bool P16>
+__device__ __forceinline__ void wave_kernel_body(const KernelArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NT = NB * (NB + 1) / 2;
   const int lane = threadIdx.x;
@@ -209,9 +211,9 @@ __global__ __launch_bounds__(64, (NB <= 5 && MODE == kModeCG) ? 3 : CUMF_WAVE_MI
     cg_wave_core<NB, 1, 0>(acc, smem, a, f, row, rowlen, lane);  // the reference's default solver (als.cu:28)
   } else {
 #if CUMF_ABLATE
-    const float ssq = lu_wave_blocked<NB, FC>(acc, smem, f, reg, a.update + (size_t)row * f, lane, a.dbg);
+    const float ssq = lu_wave_blocked<NB, FC, P16>(acc, smem, f, reg, a.update + (size_t)row * f, lane, a.dbg);
 #else
-    const float ssq = lu_wave_blocked<NB, FC>(acc, smem, f, reg, a.update + (size_t)row * f, lane);
+    const float ssq = lu_wave_blocked<NB, FC, P16>(acc, smem, f, reg, a.update + (size_t)row * f, lane);
 #endif
     constexpr float ff_sign = -1.0f;  // the blocked elimination works on the negated system
     if (a.sse_bins != nullptr) {  // fused train SSE: (f, f) of the eliminated system - reg (1 + |theta|^2)
@@ -220,6 +222,14 @@ __global__ __launch_bounds__(64, (NB <= 5 && MODE == kModeCG) ? 3 : CUMF_WAVE_MI
       wave_sse_add(a.sse_bins, (double)ff - (double)reg * (1.0 + (double)tt), rowlen, lane);
     }
   }
+}
+template <int NB, int MODE, int FC, int ARITH = kArithSplit3, bool WHOLE = false>
+__global__ __launch_bounds__(64, (NB <= 5 && MODE == kModeCG) ? 3 : CUMF_WAVE_MIN_WAVES) void als_wave_kernel(const KernelArgs a) {
+  wave_kernel_body<NB, MODE, FC, ARITH, WHOLE, MODE == kModeLU && lu16_default(NB)>(a);
+}
+template <int NB, int MODE, int FC, int ARITH, bool WHOLE>
+__global__ __launch_bounds__(64, CUMF_WAVE_MIN_WAVES) void als_wave_kernel_p4(const KernelArgs a) {
+  wave_kernel_body<NB, MODE, FC, ARITH, WHOLE, false>(a);
 }
 
 // ----------------------------------------------------------------------------------
@@ -466,23 +476,27 @@ static hipError_t with_arith(const Route& r, Go&& go) {
 #if CUMF_WAVE_PART == 1 && CUMF_WAVE_NB <= 7
 // ---- part 1: the LU form of the wave-per-item kernel
 template <int NB, int FC, int ARITH, bool WHOLE>
-static hipError_t launch_wave_lu_w(const KernelArgs& a, long n_items, hipStream_t stream) {
+static hipError_t launch_wave_lu_w(const KernelArgs& a, bool lu16, long n_items, hipStream_t stream) {
   const size_t stage_lds = wave_stage_lds_floats<NB, ARITH>() * sizeof(float);
   const size_t lu_lds = wave_lu_lds_floats<NB>(a.f) * sizeof(float);
   const size_t lds = lu_lds > stage_lds ? lu_lds : stage_lds;
+  auto kernel = als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>;
+  if constexpr (lu16_default(NB)) {
+    if (!lu16) kernel = als_wave_kernel_p4<NB, kModeLU, FC, ARITH, WHOLE>;  // CUMF_ALS_LU16=0: the four-pivot panels
+  }
   if (n_items <= 0) {  // every row of the plan went to the dual-form kernel (als_dual.hip): this is still the route's kernel
-    note_item_kernel(reinterpret_cast<const void*>(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>));
+    note_item_kernel(reinterpret_cast<const void*>(kernel));
     return hipSuccess;
   }
-  return launch_item_kernel(als_wave_kernel<NB, kModeLU, FC, ARITH, WHOLE>, dim3((unsigned)n_items), dim3(64), lds, stream, a);
+  return launch_item_kernel(kernel, dim3((unsigned)n_items), dim3(64), lds, stream, a);
 }
 // whole: no item of this launch dumps partial tiles (WHOLE: the instance without the dump exit)
 template <int NB>
 hipError_t wave_lu_launch(const KernelArgs& a, const Route& r, bool whole, long n_items, hipStream_t stream) {
   return with_arith(r, [&](auto arith, auto fc) {
     constexpr int ARITH = decltype(arith)::value, FC = decltype(fc)::value;
-    return whole ? launch_wave_lu_w<NB, FC, ARITH, true>(a, n_items, stream)
-                 : launch_wave_lu_w<NB, FC, ARITH, false>(a, n_items, stream);
+    return whole ? launch_wave_lu_w<NB, FC, ARITH, true>(a, r.lu16, n_items, stream)
+                 : launch_wave_lu_w<NB, FC, ARITH, false>(a, r.lu16, n_items, stream);
   });
 }
 #endif

@@ -8,6 +8,8 @@
 //     itself (the elimination of lu_solve_mfma, als_lu_wg.h) -- then the trailing update on the bf16 pipe (lu_trailing_mfma*).
 //     The fourth panel of a block row skips its fp32 MFMAs and leaves rows 12 .. 15 as SIDE ROWS in LDS.  Nothing waits on
 //     another wave.  Back substitution straight from the tiles through a 16-column LDS window (back_substitute_tiles).
+//     NB = 7 eliminates sixteen pivots per step instead (lu_wave_blocked16): the diagonal tile once per block row by DPP row
+//     broadcasts, the block row as T N on the bf16 pipe -- no panel-row exchange, no fp32 MFMA, no side rows.
 //   * CG on the accumulators (cg_wave_core): vectors in a column layout, the mat-vec on the upper
 //     tiles with DPP / ds_bpermute reductions, 1, 2 or 4 waves per system.
 #pragma once
@@ -107,7 +109,7 @@ __host__ __device__ constexpr int wave_lu_lds_floats(int f) {
 // fourth panel of a block row skips its fp32 MFMAs -- but in `side` as rows of W (scaled by 1 / sqrt(u_kk), rdiag holds the
 // matching reciprocal): the lanes of those rows read tile (I, kb) of the side store, one slot further per block column,
 // instead of the window (layout and banks: wave_lu_side_offset).
-template <int NB, int NQ>
+template <int NB, int NQ, bool SIDE = true>
 __device__ __forceinline__ float back_substitute_tiles(const f32x4 (&acc)[NB * (NB + 1) / 2], float* T,
                                                       const float* rdiag, const float* zpad, const float* side, int f,
                                                       float* __restrict__ x_global, int lane) {
@@ -137,7 +139,7 @@ __device__ __forceinline__ float back_substitute_tiles(const f32x4 (&acc)[NB * (
     const int ic = i < f ? i : f - 1;
     const int I = ic >> 4;
     ib[q] = i < f ? I : 1 << 20;  // rows past f never take part
-    const bool srow = I < NB - 1 && (ic & 15) >= 12;
+    const bool srow = SIDE && I < NB - 1 && (ic & 15) >= 12;
     const int tII = I * NB - I * (I - 1) / 2;  // tile_of(I, I); tile_of(I, kb) = tII + kb - I
     const float* sp = side + (tII + (NB - 1) - I) * kSideSlot + 32 * I + 12 + 16 * (tII & 1) + 17 * (ic & 3);
     rowp[q] = srow ? sp : T + ic * kBsPitch;
@@ -263,9 +265,125 @@ __device__ __forceinline__ void lu_trailing_mfma32(f32x4 (&acc)[NB * (NB + 1) / 
   if constexpr (PROD == 5) acc[t] = mfma_bf16(q(hA[I], hB[I]), q(hA[J], hB[J]), acc[t]);
 }
 
+// The same elimination with SIXTEEN pivots per step (profiles/lu16/; the default at NB = 7, CUMF_ALS_LU16=0: the four-pivot
+// panels of lu_wave_blocked; any NB and a run-time f work, NB = 5 and the dual kernel were measured slower with it).  Per
+// block row Ip
+//   1. the diagonal tile is eliminated on a copy, read as M[i = c][j = 4 g + r] (the tile is symmetric up to the rounding of
+//      its two triangles: the accumulator register is N[4 g + r][c]), by row operations: column k reaches all four lane groups
+//      with one ds_bpermute, row k with row_newbcast inside the v_fmac (lu16_row_step).  The same operations on the identity
+//      leave row c of E = L^-1 in the same layout, which IS the A-operand layout of the MFMA (lane (g, c): T[c][4 g + e]):
+//      T = diag(1 / sqrt(u_kk)) E, split exactly into h | m | l in registers (six registers: no LDS image).  A pivot past f
+//      eliminates nothing and keeps a unit scale: row f of W stays the Schur complement the fused train SSE reads;
+//   2. W(Ip, J) = T N(Ip, J) for every tile of the block row as six bf16 MFMAs (small terms first), N(Ip, J) split in
+//      registers (its C/D layout is the B-operand layout).  W = -U / sqrt(u_kk) replaces the tile -- what the side rows were:
+//      the back substitution reads every row with the reciprocal -1 / sqrt(u_kk) -- and its split is the trailing operand
+//      (K slot (g, e) = pivot 4 g + e, in both operands).
+// No panel-row exchange, no fp32 MFMA, no side store; pairs, pending rank-32 updates (one in front of each pivot step) and the
+// back substitution as in lu_wave_blocked.
 template <int NB, int FC>
+__device__ __forceinline__ float lu_wave_blocked16(f32x4 (&acc)[NB * (NB + 1) / 2], float* T, int f_rt, float reg,
+                                                   float* __restrict__ x_global, int lane) {
+  constexpr int NT = NB * (NB + 1) / 2;
+  const int f = FC ? FC : f_rt;
+  const int c = lane & 15, g = (lane >> 4) & 3;
+  static_for<NT>([&](auto tc) {
+    constexpr int t = decltype(tc)::value;
+    constexpr bool diag = tile_I<NB>(t) == tile_J<NB>(t);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = acc[t][r];
+      if constexpr (diag) v = (4 * g + r == c) ? v + reg : v;
+      acc[t][r] = -v;
+    }
+  });
+  float* rdiag = T + 16 * NB * kBsPitch;
+  float* zpad = rdiag + ((f + 3) & ~3);
+  if (lane < 16) zpad[lane] = 0.f;
+  auto bperm = [](int addr, float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
+  };
+  u32x2 hA[NB], mA[NB], lA[NB], hB[NB], mB[NB], lB[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) hA[b] = mA[b] = lA[b] = hB[b] = mB[b] = lB[b] = u32x2{0u, 0u};
+  static_for<NB>([&](auto ipc) {
+    constexpr int Ip = decltype(ipc)::value;
+    constexpr int L = NB - Ip;
+    constexpr bool FIRST = (Ip & 1) == 0;
+    constexpr int NTl = (FIRST && Ip >= 2) ? (L - 1) * L / 2 : 0;
+    constexpr int TP = 6 * NTl;
+    constexpr int SD = tile_of<NB>(Ip, Ip);
+    // ---- 1. the diagonal tile
+    float n[4], e[4], rsown = 1.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) n[r] = acc[SD][r], e[r] = (4 * g + r == c) ? 1.0f : 0.f;
+    static_for<16>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      constexpr int p = 16 * Ip + k;
+      constexpr int n0 = k * TP / 16, n1 = (k + 1) * TP / 16;
+      static_for<n1 - n0>([&](auto nc) {
+        constexpr int nn = n0 + decltype(nc)::value;
+        lu_trailing_mfma32<NB, lu_trailing_tile<NB, Ip + 1>(nn % NTl), nn / NTl>(acc, hA, mA, lA, hB, mB, lB);
+      });
+      constexpr bool dyn = FC == 0 && Ip == NB - 1;  // the pivot exists only if p < f (run time)
+      if constexpr (FC == 0 || p < FC) {  // a pivot past f eliminates nothing and keeps its row unscaled
+        const float colk = bperm(4 * (16 * (k >> 2) + c), n[k & 3]);  // M[c][k], in every lane group
+        float rs = __builtin_amdgcn_rsqf(-row_bcast<k>(colk));
+        float m = colk * (rs * rs);
+        bool act = c > k;
+        if constexpr (dyn) act = act && p < f, rs = p < f ? rs : 1.0f;
+        m = act ? m : 0.f;
+        rsown = (c == k) ? rs : rsown;
+        if constexpr (k < 15) lu16_row_step<k>(n, e, m);
+      }
+      if constexpr (TP > 0) __builtin_amdgcn_sched_barrier(0);
+    });
+    if (16 * Ip + c < f) rdiag[16 * Ip + c] = -rsown;  // the rows are rows of W: diagonal -sqrt(u_kk)
+    unsigned H0, M0, L0, H1, M1, L1;
+    split3_pair(e[0] * rsown, e[1] * rsown, H0, M0, L0);
+    split3_pair(e[2] * rsown, e[3] * rsown, H1, M1, L1);
+    const u32x2 Th = {H0, H1}, Tm = {M0, M1}, Tl = {L0, L1};
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- 2. the block row, and the update of the next block row's tiles at once
+    static_for<L>([&](auto bc2) {
+      constexpr int b = Ip + decltype(bc2)::value;
+      constexpr int t = tile_of<NB>(Ip, b);
+      split3_pair(acc[t][0], acc[t][1], H0, M0, L0);
+      split3_pair(acc[t][2], acc[t][3], H1, M1, L1);
+      const u32x2 Nh = {H0, H1}, Nm = {M0, M1}, Nl = {L0, L1};
+      f32x4 W = mfma_bf16_k16(Tl, Nh, f32x4{0.f, 0.f, 0.f, 0.f});
+      W = mfma_bf16_k16(Th, Nl, W);
+      W = mfma_bf16_k16(Tm, Nm, W);
+      W = mfma_bf16_k16(Tm, Nh, W);
+      W = mfma_bf16_k16(Th, Nm, W);
+      W = mfma_bf16_k16(Th, Nh, W);
+      acc[t] = W;
+      if constexpr (b > Ip) {
+        split3_pair(W[0], W[1], H0, M0, L0);
+        split3_pair(W[2], W[3], H1, M1, L1);
+        constexpr int tn = tile_of<NB>(Ip + 1, b);
+        if constexpr (FIRST) {
+          hA[b] = u32x2{H0, H1};
+          mA[b] = u32x2{M0, M1};
+          lA[b] = u32x2{L0, L1};
+          static_for<6>([&](auto pc) { lu_trailing_mfma<NB, tn, decltype(pc)::value>(acc, hA, mA, lA); });
+        } else {
+          hB[b] = u32x2{H0, H1};
+          mB[b] = u32x2{M0, M1};
+          lB[b] = u32x2{L0, L1};
+          static_for<6>([&](auto pc) { lu_trailing_mfma32<NB, tn, decltype(pc)::value>(acc, hA, mA, lA, hB, mB, lB); });
+        }
+      }
+    });
+    __builtin_amdgcn_sched_barrier(0);
+  });
+  __syncthreads();
+  return back_substitute_tiles<NB, (16 * NB + 63) / 64, false>(acc, T, rdiag, zpad, T, f, x_global, lane);
+}
+// P16: the sixteen-pivot panel scheme (lu_wave_blocked16) in place of the four-pivot panels below
+template <int NB, int FC, bool P16 = false>
 __device__ __forceinline__ float lu_wave_blocked(f32x4 (&acc)[NB * (NB + 1) / 2], float* T, int f_rt, float reg,
                                                  float* __restrict__ x_global, int lane, int dbg = 0) {
+  if constexpr (P16) return lu_wave_blocked16<NB, FC>(acc, T, f_rt, reg, x_global, lane);
   constexpr int NT = NB * (NB + 1) / 2;
   const int f = FC ? FC : f_rt;
   LuLaneS ln;
