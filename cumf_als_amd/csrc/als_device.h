@@ -89,6 +89,11 @@ __device__ __forceinline__ float wave_sum_uniform(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// v of the lane at byte address addr = 4 * lane (ds_bpermute on floats)
+__device__ __forceinline__ float bperm(int addr, float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
+}
+
 // Cross-lane moves and the transposing wave reduction of the Gram-free CG kernels (als_short.hip, als_implicit.hip).
 template <int CTRL, int BANK_MASK>
 __device__ __forceinline__ float dpp_move(float old, float v) {

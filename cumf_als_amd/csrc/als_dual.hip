@@ -4,7 +4,7 @@
 // wave kernel still factors the full (f + 1)-column system.  The same normal equations are solved by
 //   x = T^T y,   (T T^T + lambda n I) y = r
 // (push-through identity: T^T (T T^T + c I)^-1 = (T^T T + c I)^-1 T^T), and the n x n system K = T T^T has NBD = 5 tile
-// blocks for n <= 79 -- 15 tiles instead of 28, the elimination lu_wave_blocked<5> runs at f = 64 .. 79.  One wave per row:
+// blocks for n <= 79 -- 15 tiles instead of 28, the elimination lu_wave_blocked<5> (als_wave_lu.h, four-pivot panels) runs at f = 64 .. 79.  One wave per row:
 //   operands  K's MFMA contracts over FEATURES, and a pre-split table row is [h: 96 bf16][m][l][strip] (als_wave_pre.h): the
 //             eight K slots 8 g .. 8 g + 7 of lane (g, c) for feature chunk kc are 16 contiguous bytes of plane p of row
 //             idx[16 I + c], at byte 192 p + 64 kc + 16 g -- ONE global_load_dwordx4 per (block I, plane, chunk) straight into
@@ -30,7 +30,8 @@
 #include "als_internal.h"
 #include "als_lu_blocked.h"
 #include "als_wave_gram.h"
-#include "als_wave_solve.h"
+#include "als_wave_lu.h"
+#include "als_wave_solve.h"  // wave_sse_add
 
 namespace cumf {
 
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(64, kDualWaves) void als_dual_kernel(const KernelAr
   const float reg = (float)n * a.lambda;
   float* ybuf = smem + wave_lu_lds_floats<NBD>(kMaxN);
   if (lane < 32) ybuf[16 * (NBD - 1) + lane] = 0.f;  // y past n' reads as zero below (the LU writes y[0 .. n') behind this)
-  const float ssq = lu_wave_blocked<NBD, 0>(acc, smem, np, reg, ybuf, lane);
+  const float ssq = lu_wave_blocked<NBD, 0, kLuPanel4>(acc, smem, np, reg, ybuf, lane);
   __syncthreads();  // one wave: orders the writes of y before the reads below
   if (a.sse_bins != nullptr) {
     const float yy = wave_sum_uniform(ssq);

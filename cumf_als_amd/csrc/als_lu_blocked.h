@@ -1,6 +1,7 @@
-// als_lu_blocked.h -- the pieces of the blocked elimination (round 4: lu_wave_blocked, als_wave_solve.h): the exact bf16x3 split
+// als_lu_blocked.h -- the pieces of the blocked elimination (round 4: lu_wave_blocked, als_wave_lu.h): the exact bf16x3 split
 // (also the Gram stage's and the pre-split kernel's), the preparation of one four-pivot panel on the accumulators of ONE wave
-// (DPP quad broadcasts + ds_bpermute, no barrier), the rank-16 bf16 MFMA.  (Round 5 shared them with a row-owning workgroup
+// (DPP quad broadcasts + ds_bpermute, no barrier), one pivot step of the sixteen-pivot diagonal tile (lu16_row_step), the
+// rank-16 bf16 MFMA.  (Round 5 shared them with a row-owning workgroup
 // LU of the large systems that was built, was correct and was slower: it lives as profiles/r05/lu_rows_experiment.patch,
 // not in the tree.)
 #pragma once
@@ -118,9 +119,6 @@ __device__ __forceinline__ void lu_prep_step_s(const ACC& acc, LuPrepS<NB>& s, f
   constexpr int p0 = 16 * Ip + 4 * q;
   auto sel = [](bool p, float a, float b) { return p ? a : b; };
   auto rsq = [](float d) { return __builtin_amdgcn_rsqf(d); };
-  auto bperm = [](int addr, float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
-  };
   const bool v1 = !DYN || p0 + 1 < f, v2 = !DYN || p0 + 2 < f, v3 = !DYN || p0 + 3 < f;
   if constexpr (STEP == 0) {
     // Round 6: the panel's raw rows reach the other lane groups through LDS -- every lane stores the four rows it holds of

@@ -200,7 +200,7 @@ __device__ __forceinline__ float back_substitute_tiles_wg(const LuAcc<NB, NW>& a
   return ssq;
 }
 
-// sse_bins != nullptr: the train SSE of the row for free, as in lu_wave_blocked (als_wave.hip, wave_tile_ff): entry (f, f)
+// sse_bins != nullptr: the train SSE of the row for free, as in lu_wave_blocked (als_wave_lu.h; wave_tile_ff): entry (f, f)
 // of the eliminated system is the Schur complement sum r^2 + reg - b^T A^-1 b, so SSE = (f, f) - reg (1 + |x|^2); the role
 // that owns the last diagonal tile hands (f, f) to wave 0 through LDS.
 template <int NB, int W, int NW = 4>
@@ -364,7 +364,7 @@ __device__ __forceinline__ void lu_solve_mfma(LuAcc<NB, NW>& acc, float* __restr
 }
 
 // ----------------------------------------------------------------------------------
-// Round 6: the same elimination BLOCKED by block rows, as lu_wave_blocked (als_wave.hip) runs it inside one wave -- here over
+// Round 6: the same elimination BLOCKED by block rows, as lu_wave_blocked (als_wave_lu.h) runs it inside one wave -- here over
 // NW wave roles.  lu_solve_mfma applies every four-pivot panel to ALL live tiles with fp32 MFMAs (36 cycles each, nothing
 // issues beside them): 1 820 per 200 x 200 system, and every role forms the eliminated panel row at every feature block of
 // its tiles, panel after panel (13 x 7 VALU + 13 LDS reads per panel and role at the start).  Blocked:

@@ -80,7 +80,7 @@ static bool presplit_wanted(int f, long gather_rows, const Switches& sw) {
 //   dual rows  LU plans on one wave in the production pre-split form (kArithPrePk, f = 96 .. 111): the whole rows of
 //          1 .. kDualMaxRow ratings (the plan lists them last in every item list) solve their n x n dual system
 //          (als_dual.hip).  Rows without ratings stay (the reference's NaN).  CUMF_ALS_DUAL=0: none.
-//   lu16   the one-wave LU of NB = 7 eliminates sixteen pivots per step (lu_wave_blocked16); CUMF_ALS_LU16=0: the four-pivot
+//   lu16   the one-wave LU of NB = 7 eliminates sixteen pivots per step (kLuPanel16, als_wave_lu.h); CUMF_ALS_LU16=0: the four-pivot
 //          panels (the _p4 instances), which NB < 7 and the dual kernel keep (measured slower there: profiles/lu16/).
 //   sse    every solver but two adds the train SSE of its rows: the workgroup CG of als_reduce_kernel, and its thread-grid LU
 //          below NB = 7 -- the chunked rows of LU plans below f = 96 and of CG plans at f = 112 .. 128 are not covered.

@@ -11,7 +11,7 @@
 //     als_wave_multi_kernel (NB = 8 .. 13): two waves per item share the chunks and split the tiles.
 //   * The Gram stage -- fp32 on the bf16 matrix pipe: als_wave_gram.h (the in-kernel split of the fp32 gather table) and
 //     als_wave_pre.h (the pre-split table).
-//   * LU and CG on the accumulators, the tile epilogues: als_wave_solve.h.
+//   * The tile epilogues and the CG on the accumulators: als_wave_solve.h.  The LU on the accumulators: als_wave_lu.h.
 //
 // This file: the kernels, the body of the two-wave kernel, the launchers and the explicit instantiations of this
 // translation unit's NB and part.
@@ -101,9 +101,9 @@ __device__ __forceinline__ void fast_unscale(f32x4 (&acc)[(NB * (NB + 1) / 2 + N
 // five of them in scratch (41 spilled registers, 2.9 GB of scratch writes per Netflix Theta launch; 0 without it).
 // (the CG instances of the small systems sit at the edge of three waves per SIMD -- 166 registers at NB = 5 -- and the packed form
 // went over it: 174 registers, Theta side 4.6 -> 4.95 ms at f = 64; held at three)
-// P16: the LU eliminates sixteen pivots per step (lu_wave_blocked16) -- als_wave_kernel where lu16_default(NB) -- or four
-// (als_wave_kernel_p4: the instances CUMF_ALS_LU16=0 routes to).
-template <int NB, int MODE, int FC, int ARITH, bool WHOLE, bool P16>
+// PANEL: the LU eliminates sixteen pivots per step (kLuPanel16) -- als_wave_kernel where lu16_default(NB) -- or four
+// (kLuPanel4; als_wave_kernel_p4: the instances CUMF_ALS_LU16=0 routes to).
+template <int NB, int MODE, int FC, int ARITH, bool WHOLE, LuPanel PANEL>
 __device__ __forceinline__ void wave_kernel_body(const KernelArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NT = NB * (NB + 1) / 2;
@@ -210,11 +210,7 @@ __device__ __forceinline__ void wave_kernel_body(const KernelArgs& a) {
   } else if constexpr (MODE == kModeCG) {
     cg_wave_core<NB, 1, 0>(acc, smem, a, f, row, rowlen, lane);  // the reference's default solver (als.cu:28)
   } else {
-#if CUMF_ABLATE
-    const float ssq = lu_wave_blocked<NB, FC, P16>(acc, smem, f, reg, a.update + (size_t)row * f, lane, a.dbg);
-#else
-    const float ssq = lu_wave_blocked<NB, FC, P16>(acc, smem, f, reg, a.update + (size_t)row * f, lane);
-#endif
+    const float ssq = lu_wave_blocked<NB, FC, PANEL>(acc, smem, f, reg, a.update + (size_t)row * f, lane, a.dbg);
     constexpr float ff_sign = -1.0f;  // the blocked elimination works on the negated system
     if (a.sse_bins != nullptr) {  // fused train SSE: (f, f) of the eliminated system - reg (1 + |theta|^2)
       const float ff = ff_sign * wave_tile_ff<NB>(acc[NT - 1], f);
@@ -225,11 +221,11 @@ __device__ __forceinline__ void wave_kernel_body(const KernelArgs& a) {
 }
 template <int NB, int MODE, int FC, int ARITH = kArithSplit3, bool WHOLE = false>
 __global__ __launch_bounds__(64, (NB <= 5 && MODE == kModeCG) ? 3 : CUMF_WAVE_MIN_WAVES) void als_wave_kernel(const KernelArgs a) {
-  wave_kernel_body<NB, MODE, FC, ARITH, WHOLE, MODE == kModeLU && lu16_default(NB)>(a);
+  wave_kernel_body<NB, MODE, FC, ARITH, WHOLE, (MODE == kModeLU && lu16_default(NB)) ? kLuPanel16 : kLuPanel4>(a);
 }
 template <int NB, int MODE, int FC, int ARITH, bool WHOLE>
 __global__ __launch_bounds__(64, CUMF_WAVE_MIN_WAVES) void als_wave_kernel_p4(const KernelArgs a) {
-  wave_kernel_body<NB, MODE, FC, ARITH, WHOLE, false>(a);
+  wave_kernel_body<NB, MODE, FC, ARITH, WHOLE, kLuPanel4>(a);
 }
 
 // ----------------------------------------------------------------------------------

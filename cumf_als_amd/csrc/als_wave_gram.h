@@ -519,9 +519,6 @@ __device__ __forceinline__ float fold_strip_cols(float v, bool sp, int c) {
 template <int NB>
 __device__ __forceinline__ void wave_fold_strip(f32x4 (&acc)[NB * (NB + 1) / 2], bool sp, int lane) {
   const int c = lane & 15, g = lane >> 4;
-  auto bperm = [](int addr, float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
-  };
   static_for<NB>([&](auto ic) {
     constexpr int t = tile_of<NB>(decltype(ic)::value, NB - 1);
 #pragma unroll
