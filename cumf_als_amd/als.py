@@ -25,7 +25,9 @@
 * `update_matfree`, `matfree_available` (include/cumf_free_capi.h): the explicit half-iteration at any even 8 <= f <= 512 by a
   CG that never forms a row's system; `ALSEngine(solver="cg_matfree")` and `do_als(solver="cg_matfree")` train with it.
 * `update_weighted`, `weighted_loss`, `weighted_available` (include/cumf_weighted_capi.h): the same CG with a weight on every
-  stored entry and one weight w0 on everything unstored; `WeightedALSEngine` trains with it.
+  stored entry and one weight w0 on everything unstored; `WeightedALSEngine` trains with it.  `weighted_gram`,
+  `update_weighted_rank1`, `weighted_rank1_loss`: the same with the rank-one weight a_u c_i on the unstored entry (u, i)
+  (`WeightedALSEngine(unobserved=(a, c))`; `popularity_weights` gives eALS's c).
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -1146,16 +1148,108 @@ def weighted_loss(rowptr, colidx, val, wgt, XT, thetaT, lambda_: float, w0: floa
     return out
 
 
+def _check_rank1_vec(name, t, rows, device=None):
+    import torch
+
+    if not hasattr(t, "is_cuda") or t.dtype != torch.float32 or t.dim() != 1 or int(t.shape[0]) != int(rows) \
+            or (device is not None and t.device != device):
+        raise TypeError(f"{name} must be a float32 device tensor of length {rows}")
+    return t.contiguous()
+
+
+def weighted_gram(table, row_w, G=None):
+    """G = table^T diag(row_w) table (f x f fp32, both triangles, exactly symmetric) of a rows x f table and one weight per
+    row (cumf_weighted_gram); bit-identical run to run, and with row_w = 1 the bits of `implicit_gram`."""
+    import torch
+
+    rows, f = int(table.shape[0]), int(table.shape[1])
+    row_w = _check_rank1_vec("weighted_gram: row_w", row_w, rows, table.device)
+    if G is None:
+        G = torch.empty((f, f), dtype=torch.float32, device=table.device)
+    _libmod.check(_libmod.load().cumf_weighted_gram(_dp(table, torch.float32), _dp(row_w, torch.float32), rows, f,
+                                                    _dp(G, torch.float32), _stream()), "cumf_weighted_gram")
+    return G
+
+
+def update_weighted_rank1(plan: Plan, colidx, val, wgt, gather, G, own_w0, gather_w0, update, lambda_: float, reg="weighted",
+                          cg_iters: int = 6):
+    """`update_weighted` with the weight own_w0[u] * gather_w0[i] on the unstored entry (u, i) in place of one scalar
+    (cumf_als_update_weighted_rank1): own_w0 has one weight per row of `update` (all of them, whatever rows the plan covers),
+    gather_w0 one per row of `gather`, and G is weighted_gram(gather, gather_w0).  The same CG on
+    A v = own_w0[u] G v + T^T ((w - own_w0[u] gather_w0) o (T v)) + reg v; even 8 <= f <= 512.  With gather_w0 = 1 and
+    own_w0 = w0 the result is `update_weighted`'s, bit for bit.  Rows without entries get 0."""
+    import torch
+
+    if not weighted_available(plan.f):
+        raise ValueError(f"update_weighted_rank1 takes even 8 <= f <= 512 (got f = {plan.f})")
+    if G is None or own_w0 is None or gather_w0 is None:
+        raise ValueError("update_weighted_rank1 needs G = weighted_gram(gather, gather_w0), own_w0 and gather_w0")
+    if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
+        raise ValueError(f"update_weighted_rank1: gather and update must be [rows, {plan.f}], the plan's f "
+                         f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
+    if tuple(G.shape) != (plan.f, plan.f):
+        raise ValueError(f"update_weighted_rank1: G must be [{plan.f}, {plan.f}] (got {tuple(G.shape)})")
+    if wgt.shape != val.shape:
+        raise ValueError(f"update_weighted_rank1: wgt must be parallel to val (got {tuple(wgt.shape)}, {tuple(val.shape)})")
+    own_w0 = _check_rank1_vec("update_weighted_rank1: own_w0", own_w0, update.shape[0], update.device)
+    gather_w0 = _check_rank1_vec("update_weighted_rank1: gather_w0", gather_w0, gather.shape[0], gather.device)
+    _libmod.check(_libmod.load().cumf_als_update_weighted_rank1(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32), _dp(gather, torch.float32),
+        _dp(G, torch.float32), _dp(own_w0, torch.float32), _dp(gather_w0, torch.float32), _dp(update, torch.float32),
+        float(lambda_), _reg_id(reg), int(cg_iters), _stream()), "cumf_als_update_weighted_rank1")
+    return update
+
+
+def weighted_rank1_loss(rowptr, colidx, val, wgt, XT, thetaT, row_w0, col_w0, lambda_: float, reg="weighted", out=None):
+    """The objective with rank-one weights on the unstored entries (cumf_weighted_rank1_loss) as a 1-element fp64 tensor:
+    sum_stored w (r - x.y)^2 + sum_unstored row_w0[u] col_w0[i] (x.y)^2 + the regularisers; rowptr/colidx/val/wgt are the CSR
+    arrays on the device (rowptr int32), XT m x f, thetaT n x f, row_w0 of length m and col_w0 of length n."""
+    import torch
+
+    m, f = int(XT.shape[0]), int(XT.shape[1])
+    row_w0 = _check_rank1_vec("weighted_rank1_loss: row_w0", row_w0, m, XT.device)
+    col_w0 = _check_rank1_vec("weighted_rank1_loss: col_w0", col_w0, thetaT.shape[0], XT.device)
+    if out is None:
+        out = torch.zeros(1, dtype=torch.float64, device=XT.device)
+    _libmod.check(_libmod.load().cumf_weighted_rank1_loss(
+        _dp(rowptr, torch.int32), _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32),
+        _dp(XT, torch.float32), _dp(thetaT, torch.float32), _dp(row_w0, torch.float32), _dp(col_w0, torch.float32), m,
+        int(thetaT.shape[0]), f, float(lambda_), _reg_id(reg), _dp(out, torch.float64), _stream()), "cumf_weighted_rank1_loss")
+    return out
+
+
+def popularity_weights(r, c0: float, exponent: float = 0.5):
+    """The eALS weights of the unstored entries of each column (He et al., SIGIR 2016): c_i = c0 n_i^e / sum_j n_j^e, n_i the
+    stored entries of column i of `r` (a `datagen.Ratings`; its CSC counts), as a device fp32 tensor of length r.n that sums to
+    c0.  Torch only; pair it with a row vector, e.g. torch.ones(r.m), as WeightedALSEngine(unobserved=(row_w0, col_w0))."""
+    import torch
+
+    if not float(c0) >= 0.0:
+        raise ValueError(f"popularity_weights: c0 must be >= 0 (got {c0})")
+    counts = torch.diff(r.csc_indptr.to(torch.int64)).to(torch.float64)
+    p = counts.pow(float(exponent))
+    p = torch.where(counts > 0, p, torch.zeros_like(p))  # (0^0 = 1 is not a popularity)
+    total = p.sum()
+    if not float(total) > 0.0:
+        raise ValueError("popularity_weights: the ratings have no stored entry")
+    return (float(c0) * p / total).to(device=r.csc_indices.device, dtype=torch.float32)
+
+
 class WeightedALSEngine(_Engine):
     """Weighted ALS on one GPU: rating r_ui of `r` (a `datagen.Ratings` on the device) counts with the weight w_ui >= 0 of
     `weights` (a device tensor parallel to r.csr_data, CSR entry order), every unstored entry is a target of 0 with the weight
     w0 >= 0.  Same shape as `ALSEngine`; every half-iteration is `update_weighted` (even 8 <= f <= 512, CG only), and with
     w0 > 0 it forms G = Y^T Y of the fixed side once, before its batches.  reg "weighted" (lambda n_u, the default) or "plain".
     w = 1, w0 = 0 is ALSEngine(solver="cg_matfree"); w = 1 + alpha |r| on ratings (r > 0) with w0 = 1 is
-    ImplicitALSEngine(solver="cg_matfree")."""
+    ImplicitALSEngine(solver="cg_matfree").
+    unobserved=(row_w0, col_w0), two fp32 device tensors of lengths m and n (finite, >= 0), weighs the unstored entry (u, i)
+    by row_w0[u] col_w0[i] in place of w0 (which must then stay 0): each half forms the weighted Gram of the fixed side once
+    and is `update_weighted_rank1` (on the pair scaled so that the largest gather weight is 1), and `loss()` is
+    `weighted_rank1_loss`.  (full(m, w0), ones(n)) trains what w0 does, bit
+    for bit; `popularity_weights` gives the eALS column weights."""
 
     def __init__(self, r, weights, f: int, lambda_: float, w0: float = 0.0, reg="weighted", cg_iters: int = 6,
-                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0):
+                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, unobserved=None):
         import torch
 
         if not weighted_available(f):
@@ -1163,6 +1257,21 @@ class WeightedALSEngine(_Engine):
         self.lam, self.w0 = float(lambda_), _check_w0(w0)
         self.reg, self.cg_iters = _reg_id(reg), int(cg_iters)
         dev = r.csr_indices.device
+        self.row_w0 = self.col_w0 = None
+        if unobserved is not None:
+            if self.w0 > 0:
+                raise ValueError(f"unobserved=(row_w0, col_w0) replaces w0: pass one of them (got w0 = {self.w0})")
+            row_w0, col_w0 = unobserved
+            self.row_w0 = _check_rank1_vec("unobserved[0] (row_w0)", row_w0, r.m, dev)
+            self.col_w0 = _check_rank1_vec("unobserved[1] (col_w0)", col_w0, r.n, dev)
+            for t in (self.row_w0, self.col_w0):
+                if not bool((torch.isfinite(t) & (t >= 0)).all()):
+                    raise ValueError("the unobserved weights must be finite and >= 0")
+            # Only the products row_w0[u] col_w0[i] are the model: each half-iteration takes the pair with the largest gather
+            # weight moved into the own vector (gather / max, own * max; one rounding per weight).  A constant vector on
+            # either side is then the scalar route's w0 on both sides: own = w0, gather = 1 exactly, the bits of update_weighted.
+            self._w0_x = self._unit_gather(self.row_w0, self.col_w0)
+            self._w0_t = self._unit_gather(self.col_w0, self.row_w0)
         if not hasattr(weights, "is_cuda") or weights.device != dev or weights.dtype != torch.float32 \
                 or tuple(weights.shape) != tuple(r.csr_data.shape):
             raise TypeError("weights must be a float32 tensor on the ratings' device, parallel to r.csr_data")
@@ -1180,22 +1289,41 @@ class WeightedALSEngine(_Engine):
                              "weights in CSC order")
         self.w_csc = self.w_csr[perm].contiguous()
         self.csr_rowptr = r.csr_indptr.to(device=self.device, dtype=torch.int32).contiguous()
-        self.G = torch.empty((f, f), dtype=torch.float32, device=self.device) if self.w0 > 0 else None
+        self.G = torch.empty((f, f), dtype=torch.float32, device=self.device) \
+            if (self.w0 > 0 or self.row_w0 is not None) else None
 
-    def _half_weighted(self, plans, colidx, val, wgt, gather, update):
+    @staticmethod
+    def _unit_gather(own, gather):
+        top = gather.max()
+        if not float(top) > 0.0:  # no weight on any unstored entry
+            return own, gather
+        return (own * top).contiguous(), (gather / top).contiguous()
+
+    def _half_weighted(self, plans, colidx, val, wgt, gather, update, own_w0=None, gather_w0=None):
+        if own_w0 is not None:  # rank-one weights on the unstored entries
+            weighted_gram(gather, gather_w0, self.G)
+            for p in plans:
+                update_weighted_rank1(p, colidx, val, wgt, gather, self.G, own_w0, gather_w0, update, self.lam, self.reg,
+                                      self.cg_iters)
+            return
         if self.w0 > 0:
             implicit_gram(gather, self.G)
         for p in plans:
             update_weighted(p, colidx, val, wgt, gather, self.G, update, self.lam, self.w0, self.reg, self.cg_iters)
 
     def update_x(self):
-        self._half_weighted(self.x_plans, self.r.csr_indices, self.r.csr_data, self.w_csr, self.thetaT, self.XT)
+        self._half_weighted(self.x_plans, self.r.csr_indices, self.r.csr_data, self.w_csr, self.thetaT, self.XT,
+                            *(self._w0_x if self.row_w0 is not None else ()))
 
     def update_theta(self):
-        self._half_weighted(self.t_plans, self.r.csc_indices, self.r.csc_data, self.w_csc, self.XT, self.thetaT)
+        self._half_weighted(self.t_plans, self.r.csc_indices, self.r.csc_data, self.w_csc, self.XT, self.thetaT,
+                            *(self._w0_t if self.row_w0 is not None else ()))
 
     def loss(self) -> float:
         """The weighted objective of the current factors (fp64)."""
+        if self.row_w0 is not None:
+            return float(weighted_rank1_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.w_csr, self.XT,
+                                             self.thetaT, self.row_w0, self.col_w0, self.lam, self.reg).item())
         return float(weighted_loss(self.csr_rowptr, self.r.csr_indices, self.r.csr_data, self.w_csr, self.XT, self.thetaT,
                                    self.lam, self.w0, self.reg).item())
 

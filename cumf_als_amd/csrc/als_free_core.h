@@ -1,7 +1,8 @@
 // als_free_core.h -- the device core of the matrix-free CGs: the explicit one (als_free.hip: A_u v = T_u^T (T_u v) + reg v),
-// the implicit one (als_implicit_free.hip: A_u v = G v + T_u^T (w o (T_u v)) + reg v) and the weighted one (als_weighted.hip:
-// A_u v = w0 G v + T_u^T ((w - w0) o (T_u v)) + reg v).  T_u is the row's gathered block of factor rows.  The kernels of the
-// three files are wrappers around
+// the implicit one (als_implicit_free.hip: A_u v = G v + T_u^T (w o (T_u v)) + reg v) and the two weighted ones (als_weighted.hip:
+// A_u v = w0 G v + T_u^T ((w - w0) o (T_u v)) + reg v, and with rank-one weights a_u c_i on the unstored entries
+// A_u v = a_u G_c v + T_u^T ((w - a_u c) o (T_u v)) + reg v).  T_u is the row's gathered block of factor rows.  The kernels of
+// the three files are wrappers around
 //   free_sparse_pass  one wave per SEGMENT of a row (at most kFreeSeg entries, cut at fixed offsets from the row's start): per
 //                     block of N entries s = T v by the transposing wave reduction, then T^T s (with weights: T^T (w o s))
 //                     accumulated in entry order, written as one f-vector partial per segment; the first pass of a
@@ -30,10 +31,15 @@ constexpr int kFreeThreads = 256;  // four waves
 //   kFreeWeightNone   no weight, coefficient val;
 //   kFreeWeightAlpha  the confidence weight w = wpar |val| (wpar = alpha), coefficient (val > 0 ? 1 + w : 0);
 //   kFreeWeightArray  w = wgt[e] - wpar (wpar = w0, the weight of the unstored entries), coefficient wgt[e] val; wgt is
-//                     indexed as val.
-enum FreeWeight { kFreeWeightNone = 0, kFreeWeightAlpha = 1, kFreeWeightArray = 2 };
+//                     indexed as val;
+//   kFreeWeightRank1  w = fma(-own_w0[row], gather_w0[j], wgt[e]) (the unstored entries of row `row` and column j weigh
+//                     own_w0[row] gather_w0[j]; wpar is not read), coefficient wgt[e] val.  own_w0 is indexed as the rows of
+//                     the args (wave-uniform), gather_w0 as the rows of `gather`: one 4-byte gather by the column index the
+//                     lane holds.  With gather_w0 = 1 the weight is wgt[e] - own_w0[row] rounded once: kFreeWeightArray's.
+enum FreeWeight { kFreeWeightNone = 0, kFreeWeightAlpha = 1, kFreeWeightArray = 2, kFreeWeightRank1 = 3 };
 template <int Q, FreeWeight kWeight>
-__device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, float wpar, const float* wgt = nullptr) {
+__device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, float wpar, const float* wgt = nullptr,
+                                                 const float* own_w0 = nullptr, const float* gather_w0 = nullptr) {
   constexpr bool kWeighted = kWeight != kFreeWeightNone;
   constexpr int N = Q <= 4 ? 16 : 8;  // entries per block: N x Q <= 64 gathered values per lane (N = 32: SGPR spills)
   const int lane = threadIdx.x & 63;
@@ -52,6 +58,8 @@ __device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, fl
       v[q] = c < f ? V[(size_t)row * f + c] : 0.f;
       acc[q] = bacc[q] = 0.f;
     }
+    [[maybe_unused]] float aw = 0.f;  // kFreeWeightRank1: the row's factor of its unstored weights (uniform)
+    if constexpr (kWeight == kFreeWeightRank1) aw = own_w0[row];
     for (int s = 0; s < len; s += 64) {
       const int cnt64 = len - s < 64 ? len - s : 64;
       const bool live = lane < cnt64;
@@ -65,6 +73,11 @@ __device__ __forceinline__ void free_sparse_pass(const FreeArgs a, int first, fl
       } else if constexpr (kWeight == kFreeWeightArray) {
         const float gl = live ? wgt[begin + s + lane] : 0.f;
         wl = live ? gl - wpar : 0.f;
+        cl = gl * rl;
+      } else if constexpr (kWeight == kFreeWeightRank1) {
+        const float gl = live ? wgt[begin + s + lane] : 0.f;
+        const float cj = live ? gather_w0[jl] : 0.f;
+        wl = live ? fmaf(-aw, cj, gl) : 0.f;
         cl = gl * rl;
       }
       for (int b = 0; b < cnt64; b += N) {
@@ -201,10 +214,14 @@ __device__ __forceinline__ void free_row_update(const FreeArgs a, long long row,
 
 // ---- the row pass with G v: kFreeRows rows per workgroup of kFreeThreads.  mode 0 (after the first sparse pass):
 // r = b - A x, p = r, rs = r.r; mode 1: one CG step with A p.  last: the rows are done after this pass.  Args: FreeArgs
-// extended by G (the f x f Gram of `gather`) and reg_mode (kFreeRegPlain: reg = lambda, else (float)n lambda).  kScale: G v is multiplied by gscale as it leaves the accumulators (the weighted
-// route's w0; at gscale = 1 the product is the factor itself, bit for bit).
-template <int Q, bool kScale, class Args>
-__device__ __forceinline__ void free_gram_rows(const Args& a, float gscale, int mode, int last) {
+// extended by G (the f x f Gram of `gather`) and reg_mode (kFreeRegPlain: reg = lambda, else (float)n lambda).  kScale: what
+// G v is multiplied by as it leaves the accumulators -- nothing, gscale (the weighted route's w0; at gscale = 1 the product
+// is the factor itself, bit for bit) or row_scale[row] (the rank-one route's own_w0, indexed as the rows of the args; rows
+// beyond the block's last read nothing).
+enum FreeScale { kFreeScaleNone = 0, kFreeScaleScalar = 1, kFreeScaleRow = 2 };
+template <int Q, FreeScale kScale, class Args>
+__device__ __forceinline__ void free_gram_rows(const Args& a, float gscale, int mode, int last,
+                                               const float* row_scale = nullptr) {
   constexpr int P = 64 * Q + 4;  // LDS pitch: the 16 rows one MFMA operand reads start 4 banks apart
   __shared__ float vs[kFreeRows * P];
   const int lane = threadIdx.x & 63;
@@ -239,6 +256,16 @@ __device__ __forceinline__ void free_gram_rows(const Args& a, float gscale, int 
     }
   }
   __syncthreads();
+  [[maybe_unused]] float rsc[2][4];  // kFreeScaleRow: the scales of the eight accumulator rows this lane holds
+  if constexpr (kScale == kFreeScaleRow) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = 16 * h + 4 * (lane >> 4) + r;
+        rsc[h][r] = rr < nr ? row_scale[r0 + rr] : 0.f;
+      }
+  }
 #pragma unroll
   for (int t = 0; t < Q; ++t) {
     const int J = wave + 4 * t;
@@ -246,8 +273,12 @@ __device__ __forceinline__ void free_gram_rows(const Args& a, float gscale, int 
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          vs[(16 * h + 4 * (lane >> 4) + r) * P + 16 * J + (lane & 15)] = kScale ? acc[t][h][r] * gscale : acc[t][h][r];
+        for (int r = 0; r < 4; ++r) {
+          float g = acc[t][h][r];
+          if constexpr (kScale == kFreeScaleScalar) g = g * gscale;
+          if constexpr (kScale == kFreeScaleRow) g = g * rsc[h][r];
+          vs[(16 * h + 4 * (lane >> 4) + r) * P + 16 * J + (lane & 15)] = g;
+        }
     }
   }
   __syncthreads();

@@ -43,6 +43,11 @@ struct ImplicitArgs {
 size_t implicit_gram_part_floats(long rows, int f);
 // G (fp32, may be null) and G64 (fp64, may be null) of a rows x f table; part: implicit_gram_part_floats floats
 hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, float* G, double* G64, hipStream_t stream);
+// its last step: the slab partials summed in slab order (fp64) into both triangles of G and / or G64
+hipError_t launch_implicit_gram_reduce(const float* part, long rows, int f, float* G, double* G64, hipStream_t stream);
+// G = Y^T diag(row_w) Y, otherwise as launch_implicit_gram (at row_w = 1: its bits)
+hipError_t launch_weighted_gram(const float* Y, const float* row_w, long rows, int f, float* part, float* G, double* G64,
+                                hipStream_t stream);
 // systems of items [0, n_items) of a's lists, then the n_mrows chunked rows
 hipError_t launch_implicit_hermitian(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream);
 // the same pass in the packed output mode: the partial systems of cumf_get_hermitian_implicit_partial -- a.tt is a batch of
@@ -65,8 +70,9 @@ inline long implicit_gram_slab(int f) {
   const int FT = (f + 15) / 16;
   return FT <= 8 ? kImpGramSlab : (long)kImpGramSlab * ((FT + 7) / 8);
 }
-// The Gram partials of a table with 128 < f <= 512 (als_implicit_free.hip; launch_implicit_gram reduces them)
-hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* part, hipStream_t stream);
+// The Gram partials of a table with 128 < f <= 512 (als_implicit_free.hip; launch_implicit_gram reduces them); row_w: nullptr,
+// or the weight of each table row (launch_weighted_gram)
+hipError_t launch_implicit_gram_wide(const float* Y, const float* row_w, long rows, int f, float* part, hipStream_t stream);
 // The matrix-free CG (als_implicit_free.hip): the arguments and segments of als_free.h, plus G and the confidence weights.
 struct ImplicitFreeArgs : FreeArgs {
   const float* G;  // f x f Gram of `gather`

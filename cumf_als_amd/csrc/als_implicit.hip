@@ -21,7 +21,9 @@
 // Compiled twice (Makefile): as als_implicit_kernels.o, everything but the packed output mode, and with
 // -DCUMF_IMPLICIT_PART=1 as als_implicit_partial.o, the packed output mode alone -- the item kernel's second set of
 // instantiations, its slot reduce and the finish kernel.  An object of their own keeps the code generated for the first
-// set exactly what it was before the second existed (tools/kernels_equal.py).
+// set exactly what it was before the second existed (tools/kernels_equal.py).  For the same reason a third time, with
+// -DCUMF_IMPLICIT_PART=2 as als_implicit_wgram.o: weighted_gram_partial_kernel alone, the Gram with a weight per table row
+// (G = Y^T diag(w) Y; include/cumf_weighted_capi.h), on the stage load and the weighted stage product of the item kernel.
 #include <hip/hip_runtime.h>
 
 #include "als_device.h"
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(kImpThreads) void implicit_slot_reduce_kernel(const
   }
 }
 
-#else  // CUMF_IMPLICIT_PART == 1
+#elif CUMF_IMPLICIT_PART == 1
 // the packed output mode of the slot reduce: the upper triangle of the chunk partials summed in chunk order (fp64), with
 // lambda n on the diagonal in weighted mode; G is not read
 __global__ __launch_bounds__(kImpThreads) void implicit_slot_reduce_packed_kernel(const ImplicitArgs a) {
@@ -496,11 +498,18 @@ size_t implicit_gram_part_floats(long rows, int f) {
   return (size_t)((rows + slab - 1) / slab) * FP * FP;
 }
 
+hipError_t launch_implicit_gram_reduce(const float* part, long rows, int f, float* G, double* G64, hipStream_t stream) {
+  const long slab = implicit_gram_slab(f);
+  const int FT = (f + 15) / 16, nslab = (int)((rows + slab - 1) / slab);
+  return launch_kernel(implicit_gram_reduce_kernel, dim3(grid_for((long long)f * f, kImpThreads, 1 << 20)), dim3(kImpThreads), 0,
+                       stream, part, nslab, f, 16 * FT, G, G64);
+}
+
 hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, float* G, double* G64, hipStream_t stream) {
   const long slab = implicit_gram_slab(f);
   const int FT = (f + 15) / 16, nslab = (int)((rows + slab - 1) / slab);
   if (nslab > 0 && FT > 8) {  // 128 < f <= 512: the tiles spread over a second grid dimension (als_implicit_free.hip)
-    const hipError_t e = launch_implicit_gram_wide(Y, rows, f, part, stream);
+    const hipError_t e = launch_implicit_gram_wide(Y, nullptr, rows, f, part, stream);
     if (e != hipSuccess) return e;
   } else if (nslab > 0) {
     const hipError_t e = with_nb<1, 8>(FT, [&](auto ft) {
@@ -509,8 +518,7 @@ hipError_t launch_implicit_gram(const float* Y, long rows, int f, float* part, f
     });
     if (e != hipSuccess) return e;
   }
-  return launch_kernel(implicit_gram_reduce_kernel, dim3(grid_for((long long)f * f, kImpThreads, 1 << 20)), dim3(kImpThreads), 0,
-                       stream, (const float*)part, nslab, f, 16 * FT, G, G64);
+  return launch_implicit_gram_reduce(part, rows, f, G, G64, stream);
 }
 
 hipError_t launch_implicit_hermitian(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream) {
@@ -558,7 +566,7 @@ hipError_t launch_implicit_loss(const int* rowptr, const int* colidx, const floa
                        (int)kImpLossBlocks, Gx, Gy, f, lambda, reg_mode, out);
 }
 
-#else  // CUMF_IMPLICIT_PART == 1
+#elif CUMF_IMPLICIT_PART == 1
 
 hipError_t launch_implicit_partial(const ImplicitArgs& a, long n_items, long n_mrows, hipStream_t stream) {
   if (n_items > 0) {
@@ -579,6 +587,61 @@ hipError_t launch_implicit_finish(const float* packed, const float* G, float reg
   const long long blocks = ((long long)batch * f * f + kImpThreads - 1) / kImpThreads;
   return launch_kernel(implicit_finish_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kImpThreads), 0, stream,
                        packed, G, reg_add, tt, (long long)batch, f);
+}
+
+#else  // CUMF_IMPLICIT_PART == 2
+
+// G = Y^T diag(row_w) Y: implicit_gram_partial_kernel with the stage's weights beside it in LDS and the weighted form of the
+// stage product the item kernel uses (implicit_stage_tiles<FT, true>: the A operand of table row k is row_w[k] y_k; at
+// row_w = 1 the operand itself, so the partials are implicit_gram_partial_kernel's bits)
+template <int FT>
+__global__ __launch_bounds__(kImpThreads) void weighted_gram_partial_kernel(const float* __restrict__ Y,
+                                                                            const float* __restrict__ row_w, long long rows,
+                                                                            int f, float* __restrict__ part) {
+  constexpr int FP = 16 * FT, TPW = ImplicitTiles<FT>::TPW, NT = ImplicitTiles<FT>::NT;
+  __shared__ float ys[kImpStage * implicit_stage_pitch(FP)];
+  __shared__ float sw[kImpStage];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const ImplicitTiles<FT> T(wave);
+  f32x4 acc[TPW];
+#pragma unroll
+  for (int q = 0; q < TPW; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const long long r0 = (long long)blockIdx.x * kImpGramSlab;
+  const int n = (int)(rows - r0 < kImpGramSlab ? rows - r0 : kImpGramSlab);
+  for (int s = 0; s < n; s += kImpStage) {
+    const int cnt = n - s < kImpStage ? n - s : kImpStage;
+    __syncthreads();
+    implicit_load_stage<FP>(ys, cnt, f, [&](int r) { return Y + (size_t)(r0 + s + r) * f; });
+    if ((int)threadIdx.x < kImpStage) sw[threadIdx.x] = (int)threadIdx.x < cnt ? row_w[r0 + s + threadIdx.x] : 0.f;
+    __syncthreads();
+    implicit_stage_tiles<FT, true>(ys, sw, T, acc, wave, lane);
+  }
+  float* out = part + (size_t)blockIdx.x * FP * FP;
+#pragma unroll
+  for (int q = 0; q < TPW; ++q) {
+    if (wave + 4 * q < NT) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[(16 * T.I[q] + 4 * (lane >> 4) + r) * FP + 16 * T.J[q] + (lane & 15)] = acc[q][r];
+    }
+  }
+}
+
+// launch_implicit_gram with a weight per table row: the same slabs, stages, tile order and reduce
+hipError_t launch_weighted_gram(const float* Y, const float* row_w, long rows, int f, float* part, float* G, double* G64,
+                                hipStream_t stream) {
+  const long slab = implicit_gram_slab(f);
+  const int FT = (f + 15) / 16, nslab = (int)((rows + slab - 1) / slab);
+  if (nslab > 0 && FT > 8) {
+    const hipError_t e = launch_implicit_gram_wide(Y, row_w, rows, f, part, stream);
+    if (e != hipSuccess) return e;
+  } else if (nslab > 0) {
+    const hipError_t e = with_nb<1, 8>(FT, [&](auto ft) {
+      return launch_kernel(weighted_gram_partial_kernel<decltype(ft)::value>, dim3((unsigned)nslab), dim3(kImpThreads), 0,
+                           stream, Y, row_w, (long long)rows, f, part);
+    });
+    if (e != hipSuccess) return e;
+  }
+  return launch_implicit_gram_reduce(part, rows, f, G, G64, stream);
 }
 
 #endif  // CUMF_IMPLICIT_PART

@@ -1,5 +1,6 @@
 // als_implicit_free.hip -- implicit-feedback ALS at any even 8 <= f <= 512: the operator-only ("matrix-free") CG of
-// CUMF_SOLVER_CG_MATFREE (include/cumf_implicit_capi.h) and the Gram of tables wider than 128 features.
+// CUMF_SOLVER_CG_MATFREE (include/cumf_implicit_capi.h) and the Gram of tables wider than 128 features, plain
+// (implicit_gram_wide_kernel) and with a weight per table row (weighted_gram_wide_kernel; include/cumf_weighted_capi.h).
 //
 // The CG never forms A_u.  Each step needs, for every live row u, A_u v = G v + T_u^T (w o (T_u v)) + reg_u v (T_u the
 // row's gathered block of factor rows, w its confidence weights): the core of als_free_core.h with the weights and with G v.
@@ -76,10 +77,65 @@ __global__ __launch_bounds__(kFreeThreads) void implicit_gram_wide_kernel(const 
   }
 }
 
-hipError_t launch_implicit_gram_wide(const float* Y, long rows, int f, float* part, hipStream_t stream) {
+// ---- G = Y^T diag(row_w) Y for 128 < f <= 512 (include/cumf_weighted_capi.h): implicit_gram_wide_kernel with the A operand
+// of table row k scaled by row_w[k] (staged in LDS beside the rows) -- the same slabs, stages, tiles and k order, so that at
+// row_w = 1, where 1 y is y, the partials are its bits.  A kernel of its own, not a second instantiation of a shared body:
+// moving any part of the kernel above into a function changes the code generated for it (tools/kernels_equal.py).
+__global__ __launch_bounds__(kFreeThreads) void weighted_gram_wide_kernel(const float* __restrict__ Y,
+                                                                         const float* __restrict__ row_w, long long rows, int f,
+                                                                         int slab, float* __restrict__ part) {
+  constexpr int TPW = kGramGroup / 4;
+  __shared__ float ys[kGramStage * kGramPitch];
+  __shared__ float sw[kGramStage];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int FT = (f + 15) / 16, FP = 16 * FT, NT = FT * (FT + 1) / 2;
+  const int t0 = (int)blockIdx.y * kGramGroup + wave;
+  int I[TPW], J[TPW];
+  f32x4 acc[TPW];
+#pragma unroll
+  for (int q = 0; q < TPW; ++q) {
+    I[q] = J[q] = 0;
+    if (t0 + 4 * q < NT) free_upper_tile(t0 + 4 * q, FT, I[q], J[q]);
+    acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const long long r0 = (long long)blockIdx.x * slab;
+  const int n = (int)(rows - r0 < slab ? rows - r0 : slab);
+  for (int s = 0; s < n; s += kGramStage) {
+    const int cnt = n - s < kGramStage ? n - s : kGramStage;
+    __syncthreads();
+    for (int e = threadIdx.x; e < kGramStage * FP; e += kFreeThreads) {
+      const int r = e / FP, c = e - r * FP;
+      ys[r * kGramPitch + c] = (r < cnt && c < f) ? Y[(size_t)(r0 + s + r) * f + c] : 0.f;
+    }
+    if ((int)threadIdx.x < kGramStage) sw[threadIdx.x] = (int)threadIdx.x < cnt ? row_w[r0 + s + threadIdx.x] : 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < kGramStage / 4; ++kk) {
+      const float* yk = ys + (4 * kk + (lane >> 4)) * kGramPitch + (lane & 15);
+      const float wk = sw[4 * kk + (lane >> 4)];
+#pragma unroll
+      for (int q = 0; q < TPW; ++q)
+        if (t0 + 4 * q < NT) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wk * yk[16 * I[q]], yk[16 * J[q]], acc[q], 0, 0, 0);
+    }
+  }
+  float* out = part + (size_t)blockIdx.x * FP * FP;
+#pragma unroll
+  for (int q = 0; q < TPW; ++q) {
+    if (t0 + 4 * q < NT) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[(16 * I[q] + 4 * (lane >> 4) + r) * FP + 16 * J[q] + (lane & 15)] = acc[q][r];
+    }
+  }
+}
+
+// row_w: nullptr for G = Y^T Y, else the weight of each table row
+hipError_t launch_implicit_gram_wide(const float* Y, const float* row_w, long rows, int f, float* part, hipStream_t stream) {
   const int FT = (f + 15) / 16, NT = FT * (FT + 1) / 2;
   const long slab = implicit_gram_slab(f);
   const unsigned nslab = (unsigned)((rows + slab - 1) / slab), groups = (unsigned)((NT + kGramGroup - 1) / kGramGroup);
+  if (row_w)
+    return launch_kernel(weighted_gram_wide_kernel, dim3(nslab, groups), dim3(kFreeThreads), 0, stream, Y, row_w,
+                         (long long)rows, f, (int)slab, part);
   return launch_kernel(implicit_gram_wide_kernel, dim3(nslab, groups), dim3(kFreeThreads), 0, stream, Y, (long long)rows, f,
                        (int)slab, part);
 }
@@ -93,7 +149,7 @@ __global__ __launch_bounds__(kFreeThreads) void implicit_free_sparse_kernel(cons
 // mode 1: one CG step with A p.  last: the rows are done after this pass.
 template <int Q>
 __global__ __launch_bounds__(kFreeThreads) void implicit_free_row_kernel(const ImplicitFreeArgs a, int mode, int last) {
-  free_gram_rows<Q, false>(a, 1.f, mode, last);
+  free_gram_rows<Q, kFreeScaleNone>(a, 1.f, mode, last);
 }
 
 hipError_t launch_implicit_free_pass(const ImplicitFreeArgs& a, int step, int cg_iters, hipStream_t stream) {

@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace cumf {
 
 constexpr int kLossThreads = 256;  // four waves
@@ -24,7 +26,7 @@ __device__ __forceinline__ double loss_block_sum(double v, double* red) {
 
 // part[block] = sum over its rows' stored entries k of term(k, s) (+ lambda (|x_u|^2 + |y_i|^2) when reg_per_entry: sum_u
 // lambda n_u |x_u|^2 = sum over the stored entries of lambda |x_u|^2, the same for Y).  One wave per row, rows strided over
-// the grid, so the sum does not depend on the device.
+// the grid, so the sum does not depend on the device.  A term that takes three arguments gets the row too: term(u, k, s).
 template <class Term>
 __device__ __forceinline__ void loss_sparse_pass(const int* __restrict__ rowptr, const int* __restrict__ colidx,
                                                  const float* __restrict__ XT, const float* __restrict__ thetaT, long long m,
@@ -45,7 +47,10 @@ __device__ __forceinline__ void loss_sparse_pass(const int* __restrict__ rowptr,
         xx = fma(xc, xc, xx);
         yy = fma(yc, yc, yy);
       }
-      acc += term(k, s);
+      if constexpr (std::is_invocable_v<Term, long long, long long, double>)
+        acc += term(u, k, s);
+      else
+        acc += term(k, s);
       if (reg_per_entry) acc += lam * (xx + yy);
     }
   }

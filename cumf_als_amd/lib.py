@@ -136,6 +136,9 @@ WEIGHTED_ABI = {
     "cumf_weighted_available": (_i, [_i]),
     "cumf_als_update_weighted": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _vp]),
     "cumf_weighted_loss": (_i, [_ip, _ip, _fp, _fp, _fp, _fp, _l, _l, _i, _f, _f, _i, _vp, _vp]),
+    "cumf_weighted_gram": (_i, [_fp, _fp, _l, _i, _fp, _vp]),
+    "cumf_als_update_weighted_rank1": (_i, [_vp, _ip, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _i, _i, _vp]),
+    "cumf_weighted_rank1_loss": (_i, [_ip, _ip, _fp, _fp, _fp, _fp, _fp, _fp, _l, _l, _i, _f, _i, _vp, _vp]),
 }
 ABI_BY_HEADER = {"cumf_als_capi.h": C_ABI, "cumf_dist_capi.h": DIST_ABI, "cumf_implicit_capi.h": IMPLICIT_ABI,
                  "cumf_topk_capi.h": TOPK_ABI, "cumf_nnls_capi.h": NNLS_ABI, "cumf_rank_capi.h": RANK_ABI,

@@ -1,6 +1,7 @@
 /*
  * cumf_weighted_capi.h -- C ABI of the weighted ALS of libALS.so: a weight on every stored entry and one weight on
- * everything unstored, at any even 8 <= f <= 512, without ever forming a row's f x f system.
+ * everything unstored (or, at the end of this file, a rank-one weight a_u c_i on the unstored entry (u, i)), at any even
+ * 8 <= f <= 512, without ever forming a row's f x f system.
  *
  * A stored entry (u, i) has the rating r_ui and the weight w_ui >= 0; every unstored entry has the target 0 and the weight
  * w0 >= 0.  The objective is
@@ -56,6 +57,41 @@ int cumf_als_update_weighted(const cumf_plan_t* plan, const int* colidx, const f
 int cumf_weighted_loss(const int* rowptr, const int* colidx, const float* val, const float* wgt, const float* XT,
                        const float* thetaT, long m, long n, int f, float lambda, float w0, int reg_mode, double* out,
                        void* stream);
+
+/* ---- Rank-one weights on the unstored entries: the unstored entry (u, i) weighs a_u c_i (a >= 0 of length m, c >= 0 of length
+ * n) in place of the one scalar w0 -- eALS's popularity weights c_i = c0 n_i^e / sum_j n_j^e (He et al., SIGIR 2016) with a = 1,
+ * per-user exposure weights with c = 1, w0 itself with a = w0, c = 1.
+ *   L = sum_stored w (r - x_u . y_i)^2 + sum_unstored a_u c_i (x_u . y_i)^2 + sum_u reg_u |x_u|^2 + sum_i reg_i |y_i|^2,
+ *   A_u = a_u G_c + sum_{i in R(u)} (w_ui - a_u c_i) y_i y_i^T + reg_u I,   G_c = Y^T diag(c) Y,   b_u = sum w r y,
+ * and the mirror image on the other side (A_i = c_i G_a + sum (w - a_u c_i) x x^T + reg_i I, G_a = X^T diag(a) X).  A
+ * half-iteration therefore takes an OWN weight vector, indexed as the rows of `update`, and a GATHER weight vector, indexed
+ * as the rows of `gather`; G is the Gram of `gather` weighted by the gather vector.  A_u = a_u sum_unstored c y y^T +
+ * sum_stored w y y^T + reg I is positive definite although w - a_u c_i may be negative.  The kernels evaluate
+ *   A_u v = a_u (G_c v) + T_u^T ((w - a_u c) o (T_u v)) + reg_u v:
+ * per stored entry and pass one more 4-byte gather (c_i, by the column index already held) than cumf_als_update_weighted, and
+ * one scale per row of G_c v.  With gather_w0 = 1 and own_w0 = w0 every pass returns the bits of cumf_als_update_weighted. */
+
+/* G = sum_k row_w[k] y_k y_k^T (f x f fp32, both triangles, exactly symmetric) of the rows x f table: cumf_implicit_gram with
+ * the weight of table row k on one operand -- the same slabs, stages, tile order and fp64 slab reduction; with row_w = 1 its
+ * bits.  row_w >= 0 and finite is the caller's contract.  Refused with hipErrorInvalidValue: f odd, below 8 or above 512,
+ * rows < 0, a NULL G, a NULL table or row_w with rows > 0. */
+int cumf_weighted_gram(const float* table, const float* row_w, long rows, int f, float* G, void* stream);
+
+/* cumf_als_update_weighted with the weight own_w0[u] gather_w0[i] on the unstored entry (u, i).  own_w0: one weight per row of
+ * `update` (ALL its rows, indexed by absolute row whatever rows the plan covers); gather_w0: one per row of `gather`; G:
+ * cumf_weighted_gram(gather, gather_w0).  The weights are the caller's contract (>= 0, finite) and are not scanned.  Refused
+ * with hipErrorInvalidValue before any device call: a NULL plan or pointer (G, own_w0 and gather_w0 are all required), a plan
+ * whose f is odd, below 8 or above 512, an unknown reg_mode. */
+int cumf_als_update_weighted_rank1(const cumf_plan_t* plan, const int* colidx, const float* val, const float* wgt,
+                                   const float* gather, const float* G, const float* own_w0, const float* gather_w0,
+                                   float* update, float lambda, int reg_mode, int cg_iters, void* stream);
+
+/* The objective L above on the CSR arrays, row_w0 = a (m) and col_w0 = c (n), as one fp64 value in out[0] (device).  Evaluated as
+ *   sum_stored [w (r - s)^2 - a_u c_i s^2] + <X^T diag(a) X, Y^T diag(c) Y>_F + regs,   s = x_u . y_i,
+ * in fp64 with fixed-order sums (the fp64 output of cumf_weighted_gram's reduction): never m x n. */
+int cumf_weighted_rank1_loss(const int* rowptr, const int* colidx, const float* val, const float* wgt, const float* XT,
+                             const float* thetaT, const float* row_w0, const float* col_w0, long m, long n, int f,
+                             float lambda, int reg_mode, double* out, void* stream);
 
 #ifdef __cplusplus
 }
