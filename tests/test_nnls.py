@@ -1,5 +1,8 @@
 """Non-negative least squares without a GPU: the C ABI of include/cumf_nnls_capi.h is exported and listed, its scope
-checks, and self-checks of the fp64 reference (tests/nnls_ref.py) that tests/test_nnls_gpu.py measures against."""
+checks, and self-checks of the fp64 reference (tests/nnls_ref.py) that tests/test_nnls_gpu.py measures against: the
+reference itself, its step-by-step trace, and the cycling fixture of tests/golden with the conditions under which
+tests/test_nnls_seams_gpu.py may expect the GPU solver to take exactly the trace's steps."""
+import importlib.util
 import os
 import re
 
@@ -9,6 +12,7 @@ import pytest
 from tests import nnls_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 HIP_INVALID_VALUE = 1
 
 
@@ -65,6 +69,121 @@ def test_reference_matches_brute_force(f):
         xb = ref.brute_force(A, b)
         assert np.abs(x - xb).max() <= 1e-10 * max(1.0, np.abs(xb).max()), (f, x, xb)
         assert (x >= 0).all() and not (x[~F] != 0).any()
+
+
+@pytest.mark.parametrize("f", [1, 2, 3, 5, 8, 10])
+def test_trace_ends_where_the_reference_ends(f):
+    """nnls_trace (signs against zero) on the brute-force cases: nnls's (x, F), consistent per-step records, and a warm
+    start from the final passive set converges in one step."""
+    rng = np.random.RandomState(f)
+    for _ in range(20):
+        A, b = _case(rng, f)
+        x, F = ref.nnls(A, b)
+        t = ref.nnls_trace(A, b)
+        assert t.converged and np.array_equal(t.F, F) and np.array_equal(t.x, x), (f, t.F, F)
+        assert not t.steps[0].F.any() and not t.steps[-1].V.any() and t.margin > 0
+        assert t.factorisations == sum(bool(s.F.any()) for s in t.steps)
+        for s, nxt in zip(t.steps, t.steps[1:]):
+            flip = s.F ^ nxt.F
+            assert s.V.any()
+            if s.murty:
+                assert flip.sum() == 1 and flip[s.index] and s.index == np.nonzero(s.V)[0].max()
+            else:
+                assert np.array_equal(flip, s.V) and s.index is None
+        w = ref.nnls_trace(A, b, F0=F)
+        assert w.converged and len(w.steps) == 1 and w.factorisations == int(F.any()) and np.array_equal(w.x, x)
+        assert not ref.nnls_trace(A, b, max_steps=1).converged or len(t.steps) == 1
+
+
+def _generator():
+    spec = importlib.util.spec_from_file_location("make_nnls_cycling", os.path.join(GOLDEN, "make_nnls_cycling.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+def _cycling_traces():
+    fx = ref.load_cycling()
+    return fx, [ref.nnls_trace(A, b) for A, b in zip(fx["A"], fx["b"])]
+
+
+def test_cycling_fixture_meets_its_conditions():
+    """Every case of tests/golden/nnls_cycling.npz is the draw its generator says, and its fp64 trace from a cold start
+    converges, takes a Murty step, has margin >= 2e-3 and cond_2(A) <= 2e3; the recorded counts are the trace's."""
+    gen = _generator()
+    fx, traces = _cycling_traces()
+    assert fx["A"].dtype == np.float32 and fx["b"].dtype == np.float32 and fx["A"].shape[1:] == (8, 8)
+    murty = np.array([sum(s.murty for s in t.steps) for t in traces])
+    assert len(traces) >= 12 and (murty >= 3).sum() >= 3, murty
+    for k, t in enumerate(traces):
+        A, b = gen.draw(int(fx["draw"][k]))
+        assert np.array_equal(A, fx["A"][k]) and np.array_equal(b, fx["b"][k]), k
+        assert np.array_equal(A, A.T)
+        assert t.converged and murty[k] >= 1 and t.margin >= gen.MARGIN, (k, t.margin)
+        assert np.linalg.cond(A.astype(np.float64), 2) <= gen.COND, k
+        assert gen.accept(A, b) is not None
+        assert (len(t.steps), murty[k], t.factorisations) == (fx["steps"][k], fx["murty_steps"][k], fx["factorisations"][k])
+        assert t.margin == fx["margin"][k]
+    assert os.path.getsize(os.path.join(GOLDEN, "nnls_cycling.npz")) < 16384
+
+
+def test_cycling_writer_is_deterministic(tmp_path):
+    """The fixture file is its arrays alone (no clock, no compression): written again, the same bytes."""
+    gen = _generator()
+    fx = ref.load_cycling()
+    p = tmp_path / "again.npz"
+    gen.write_npz(str(p), {k: fx[k] for k in fx.files})
+    assert p.read_bytes() == open(os.path.join(GOLDEN, "nnls_cycling.npz"), "rb").read()
+
+
+def test_cycling_cases_need_the_backup_rule():
+    """What makes the exact factorisation count of the GPU tests a test of Murty's rule: with the rule disabled (always
+    the full exchange) a case either never converges or takes another number of factorisations."""
+    fx, traces = _cycling_traces()
+    keep = ref.cycling_needs_murty()
+    assert len(keep) == len(traces) and keep.sum() >= 10, keep
+    for k, t in enumerate(traces):
+        u = ref.nnls_trace(fx["A"][k], fx["b"][k], murty=False)
+        assert keep[k] == (not u.converged or u.factorisations != t.factorisations)
+        assert not any(s.murty for s in u.steps)
+    print(f"{int(keep.sum())} of {len(keep)} cases tell the schedules apart")
+
+
+def test_cycling_pairs_reach_both_forms_of_the_murty_step():
+    """The GPU solver keeps the infeasible set in two words, V0 for indices below 64 and V1 from 64 on, and its Murty
+    step takes the top bit of V1, or of V0 when V1 is empty.  The embeddings put every Murty flip of the fixture in V0
+    (block below 64), in V1 (block from 64 on), and at o = 60 some in each."""
+    _, traces = _cycling_traces()
+    flips = [s.index for t in traces for s in t.steps if s.murty]
+    pairs = ref.CYCLING_PAIRS
+    assert all(o + 8 <= f for f, o in pairs)
+    assert any(o + 8 <= 64 for _, o in pairs) and any(o >= 64 for _, o in pairs)
+    across = [o for _, o in pairs if o < 64 < o + 8]
+    assert across and all(min(flips) + o < 64 <= max(flips) + o for o in across)
+
+
+@pytest.mark.parametrize("f,o", ref.CYCLING_PAIRS)
+def test_cycling_embedding_keeps_the_schedule(f, o):
+    """The embedded system takes exactly the block's steps, in fp64 and in the fp32 emulation of the GPU solver's step:
+    the same passive sets, Murty indices (shifted by o) and factorisation count, nothing outside the block ever moves."""
+    fx, traces = _cycling_traces()
+    for k, t in enumerate(traces):
+        A, b = ref.embed(fx["A"][k], fx["b"][k], f, o)
+        assert A.dtype == np.float32 and np.array_equal(A, A.T)
+        assert A.diagonal().max() == fx["A"][k].diagonal().max() and np.abs(b).max() == np.abs(fx["b"][k]).max()
+        for what, e in (("fp64", ref.nnls_trace(A, b)), ("fp32", ref.nnls_trace_fp32(A, b))):
+            assert e.converged and len(e.steps) == len(t.steps) and e.factorisations == t.factorisations, (what, k)
+            for se, sb in zip(e.steps, t.steps):
+                inside = np.zeros(f, bool)
+                inside[o:o + 8] = True
+                assert not se.F[~inside].any() and not se.V[~inside].any(), (what, k)
+                assert np.array_equal(se.F[inside], sb.F) and np.array_equal(se.V[inside], sb.V), (what, k)
+                assert se.murty == sb.murty and se.index == (o + sb.index if sb.murty else None), (what, k)
+            assert np.array_equal(e.F[o:o + 8], t.F)
+        e = ref.nnls_trace(A, b)
+        assert np.array_equal(e.x[o:o + 8], t.x)  # the same 8 x 8 solves
+        # outside the block |y| / s = c / s; inside, y = A x - b is summed over f terms instead of 8
+        assert 2e-3 <= e.margin <= t.margin * (1 + 1e-12), (k, e.margin, t.margin)
 
 
 @pytest.mark.parametrize("f", [4, 16, 50])
