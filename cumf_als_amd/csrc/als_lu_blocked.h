@@ -221,40 +221,48 @@ __device__ __forceinline__ float row_bcast(float v) {
 // DPP read of m's neighbours' registers behind their VALU writes).
 // Only the registers that some lane group still needs: column 4 g + r of M is live for 4 g + r > K (r > K - 12 at g = 3), column
 // 4 g + r of row K of E is non-zero for 4 g + r <= K (r <= K at g = 0).
+// col[0 .. 3]: the copies of columns 4 G .. 4 G + 3 of M, G = K >> 2, that EVERY lane group holds since the exchange of step
+// 4 G (lane c: M[c][4 G + j]).  The copies of the columns behind K take the step too: lane K of a copy is M[K][4 G + j], so the
+// v_fmac on the copy has the operands of the one on the owning lane group's register and leaves the same bits -- pivot steps
+// 4 G + 1 .. 4 G + 3 need no exchange.  Nobody reads the registers n of lane group 3 after the last exchange: from K = 12 on
+// only the copies and E take the step.
 // ONE asm block per step: no register is written and then read through DPP inside it, and the s_nop pair at its head covers
 // the two wait states a DPP read needs behind any VALU write in front of the block (inline asm is opaque to the hazard
-// recogniser).  The register the next step's ds_bpermute reads goes first.
+// recogniser).  What the next step reads goes first: the copy of its column, or in front of an exchange the registers n.
 template <int K>
-__device__ __forceinline__ void lu16_row_step(float (&n)[4], float (&e)[4], float m) {
+__device__ __forceinline__ void lu16_row_step(float (&n)[4], float (&e)[4], float (&col)[4], float m) {
   static_assert(K >= 0 && K < 15, "the last pivot eliminates nothing");
-  constexpr int NN = K < 12 ? 4 : 15 - K, NE = K < 3 ? K + 1 : 4, NR = NN + NE;
-  float* p[8];
+  constexpr int NC = 3 - (K & 3), NN = K < 12 ? 4 : 0, NE = K < 3 ? K + 1 : 4, NR = NC + NN + NE;
+  float* p[11];
   int cnt = 0;
-  p[cnt++] = &n[(K + 1) & 3];
-  static_for<4>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if constexpr (r > K - 12 && r != ((K + 1) & 3)) p[cnt++] = &n[r];
-  });
-  static_for<4>([&](auto rc) {
-    constexpr int r = decltype(rc)::value;
-    if constexpr (r <= K) p[cnt++] = &e[r];
-  });
+  static_for<NC>([&](auto jc) { p[cnt++] = &col[(K & 3) + 1 + decltype(jc)::value]; });
+  static_for<NN>([&](auto rc) { p[cnt++] = &n[decltype(rc)::value]; });
+  static_for<NE>([&](auto rc) { p[cnt++] = &e[decltype(rc)::value]; });
 #define CUMF_LU16_F(i) "v_fmac_f32_dpp %" #i ", %" #i ", %[m] row_newbcast:%[k] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 #define CUMF_LU16_5 CUMF_LU16_F(0) CUMF_LU16_F(1) CUMF_LU16_F(2) CUMF_LU16_F(3) CUMF_LU16_F(4)
-  if constexpr (NR == 5)
-    asm("s_nop 1\n\t" CUMF_LU16_5 : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]) : [m] "v"(m), [k] "n"(K));
-  if constexpr (NR == 6)
-    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5)
-        : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]), "+v"(*p[5])
-        : [m] "v"(m), [k] "n"(K));
+#define CUMF_LU16_O5 "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4])
+  if constexpr (NR == 5) asm("s_nop 1\n\t" CUMF_LU16_5 : CUMF_LU16_O5 : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 6) asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) : CUMF_LU16_O5, "+v"(*p[5]) : [m] "v"(m), [k] "n"(K));
   if constexpr (NR == 7)
-    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6)
-        : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]), "+v"(*p[5]), "+v"(*p[6])
-        : [m] "v"(m), [k] "n"(K));
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6) : CUMF_LU16_O5, "+v"(*p[5]), "+v"(*p[6]) : [m] "v"(m), [k] "n"(K));
   if constexpr (NR == 8)
     asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6) CUMF_LU16_F(7)
-        : "+v"(*p[0]), "+v"(*p[1]), "+v"(*p[2]), "+v"(*p[3]), "+v"(*p[4]), "+v"(*p[5]), "+v"(*p[6]), "+v"(*p[7])
+        : CUMF_LU16_O5, "+v"(*p[5]), "+v"(*p[6]), "+v"(*p[7])
         : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 9)
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6) CUMF_LU16_F(7) CUMF_LU16_F(8)
+        : CUMF_LU16_O5, "+v"(*p[5]), "+v"(*p[6]), "+v"(*p[7]), "+v"(*p[8])
+        : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 10)
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6) CUMF_LU16_F(7) CUMF_LU16_F(8) CUMF_LU16_F(9)
+        : CUMF_LU16_O5, "+v"(*p[5]), "+v"(*p[6]), "+v"(*p[7]), "+v"(*p[8]), "+v"(*p[9])
+        : [m] "v"(m), [k] "n"(K));
+  if constexpr (NR == 11)
+    asm("s_nop 1\n\t" CUMF_LU16_5 CUMF_LU16_F(5) CUMF_LU16_F(6) CUMF_LU16_F(7) CUMF_LU16_F(8) CUMF_LU16_F(9) CUMF_LU16_F(10)
+        : CUMF_LU16_O5, "+v"(*p[5]), "+v"(*p[6]), "+v"(*p[7]), "+v"(*p[8]), "+v"(*p[9]), "+v"(*p[10])
+        : [m] "v"(m), [k] "n"(K));
+  static_assert(NR >= 5 && NR <= 11, "every count has its asm block");
+#undef CUMF_LU16_O5
 #undef CUMF_LU16_5
 #undef CUMF_LU16_F
 }

@@ -279,8 +279,10 @@ __device__ __forceinline__ float lu_skip_back_substitution(const f32x4 (&acc)[NB
 // ---- kLuPanel16: the same elimination with SIXTEEN pivots per step (profiles/lu16/; the default at NB = 7; any NB and a
 // run-time f work, NB = 5 and the dual kernel were measured slower with it).  Per block row Ip
 //   1. the diagonal tile is eliminated on a copy, read as M[i = c][j = 4 g + r] (the tile is symmetric up to the rounding of
-//      its two triangles: the accumulator register is N[4 g + r][c]), by row operations: column k reaches all four lane groups
-//      with one ds_bpermute, row k with row_newbcast inside the v_fmac (lu16_row_step).  The same operations on the identity
+//      its two triangles: the accumulator register is N[4 g + r][c]), by row operations: columns 4 G .. 4 G + 3, the four
+//      registers of lane group G, reach all four lane groups with four independent ds_bpermute at pivot step 4 G and take
+//      the next three steps as copies (bit for bit what the owner holds; one LDS round trip in the dependency chain per FOUR
+//      pivots: profiles/lu16_exchange/), row k with row_newbcast inside the v_fmac (lu16_row_step).  The same operations on the identity
 //      leave row c of E = L^-1 in the same layout, which IS the A-operand layout of the MFMA (lane (g, c): T[c][4 g + e]):
 //      T = diag(1 / sqrt(u_kk)) E, split exactly into h | m | l in registers (six registers: no LDS image).  A pivot past f
 //      eliminates nothing and keeps a unit scale: row f of W stays the Schur complement the fused train SSE reads;
@@ -306,7 +308,7 @@ __device__ __forceinline__ float lu_wave_blocked16(f32x4 (&acc)[NB * (NB + 1) / 
     constexpr int L = NB - Ip;
     constexpr int SD = tile_of<NB>(Ip, Ip);
     // ---- 1. the diagonal tile
-    float n[4], e[4], rsown = 1.0f;
+    float n[4], e[4], col[4] = {0.f, 0.f, 0.f, 0.f}, rsown = 1.0f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) n[r] = acc[SD][r], e[r] = (4 * g + r == c) ? 1.0f : 0.f;
     static_for<16>([&](auto kc) {
@@ -315,14 +317,24 @@ __device__ __forceinline__ float lu_wave_blocked16(f32x4 (&acc)[NB * (NB + 1) / 
       lu_pending<NB, Ip, k, 16>(acc, hA, mA, lA, hB, mB, lB);
       constexpr bool dyn = FC == 0 && Ip == NB - 1;  // the pivot exists only if p < f (run time)
       if constexpr (FC == 0 || p < FC) {  // a pivot past f eliminates nothing and keeps its row unscaled
-        const float colk = bperm(4 * (16 * (k >> 2) + c), n[k & 3]);  // M[c][k], in every lane group
+        if constexpr ((k & 3) == 0) {  // columns k .. k + 3, the four registers of lane group k >> 2, in every lane group
+#if CUMF_ABLATE
+          if (dbg & 16384) {  // profiling build: 16384 = no column exchange (every lane group takes its own registers)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) col[r] = n[r];
+          } else
+#endif
+#pragma unroll
+          for (int r = 0; r < 4; ++r) col[r] = bperm(4 * (16 * (k >> 2) + c), n[r]);
+        }
+        const float colk = col[k & 3];  // M[c][k]
         float rs = __builtin_amdgcn_rsqf(-row_bcast<k>(colk));
         float m = colk * (rs * rs);
         bool act = c > k;
         if constexpr (dyn) act = act && p < f, rs = p < f ? rs : 1.0f;
         m = act ? m : 0.f;
         rsown = (c == k) ? rs : rsown;
-        if constexpr (k < 15) lu16_row_step<k>(n, e, m);
+        if constexpr (k < 15) lu16_row_step<k>(n, e, col, m);
       }
       if constexpr (lu_pending_mfmas<NB, Ip>() > 0) __builtin_amdgcn_sched_barrier(0);
     });
@@ -359,7 +371,8 @@ __device__ __forceinline__ float lu_wave_blocked16(f32x4 (&acc)[NB * (NB + 1) / 
 
 // The one-wave LU with the panels of PANEL; returns this lane's share of ||x||^2.  kLuPanel16 hands over to lu_wave_blocked16;
 // the body is kLuPanel4: every block row by four 4-pivot panels (lu_prep_step_s, als_lu_blocked.h).  dbg: the profiling
-// build's switches (CUMF_ABLATE): 1024 and 2048 act on both schemes, 256, 512 and those of lu_prep_step_s on kLuPanel4 only.
+// build's switches (CUMF_ABLATE): 1024 and 2048 act on both schemes, 256, 512 and those of lu_prep_step_s on kLuPanel4 only,
+// 16384 on kLuPanel16 only.
 // (The two schemes stay two whole functions, kLuPanel4 at this call depth, with plain arrays and pointers: a shared driver,
 // a block row as a function of its own, the planes or the window pointers as a struct each compiled some NB = 7 kernel to
 // other code -- profiles/lu_skeleton/.)

@@ -21,7 +21,8 @@ def main() -> int:
     ap.add_argument("--extra", type=int, nargs="*", default=[],
                     help="further solve-only runs with these LU ablation bits OR-ed to 2 (256 no panel preparation, 512 no fp32 "
                          "MFMAs, 1024 no trailing update, 2048 no back substitution)")
-    ap.add_argument("--raw", type=int, nargs="*", default=[], help="further runs with exactly these switch values")
+    ap.add_argument("--raw", type=int, nargs="*", default=[], help="further runs with exactly these switch values (16384: the "
+                    "sixteen-pivot steps of the one-wave LU without their column exchange)")
     ap.add_argument("--only", default="", help="run just this variant (full / gram_only / solve_only): for counter passes, whose "
                     "per-kernel means must not mix the variants; the warm-up iteration then runs with the other solver")
     ap.add_argument("--shape", default="netflix", help="netflix | hugewiki (the 1/8 row slab one GPU holds)")
