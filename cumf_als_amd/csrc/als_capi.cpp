@@ -302,6 +302,15 @@ extern "C" int cumf_unpack_upper(const float* packed, float* full, long batch, i
 
 extern "C" int cumf_sse(const float* val, const int* row, const int* col, const float* thetaT, const float* XT,
                         long count, int f, int surpass_nan, double* sse_out, void* stream) {
+  // sse_kernel gathers the factor rows in 8-byte pairs: an odd f would misalign every other row and read one float past
+  // the last one.  f = 0 is the sum of val^2 (doALS takes it once); the index arrays are still dereferenced then.
+  const bool reads = count > 0;
+  if (f < 0 || (f % 2) != 0 || count < 0 || !sse_out || (reads && (!val || !row || !col)) ||
+      (reads && f > 0 && (!thetaT || !XT))) {
+    fprintf(stderr, "cumf_sse: needs an even f >= 0 (got f = %d), count >= 0 (got %ld), sse_out, and for count > 0 val, row, "
+                    "col and (f > 0) both tables\n", f, count);
+    return (int)hipErrorInvalidValue;
+  }
   CUMF_HIP_CHECK(launch_sse(val, row, col, thetaT, XT, count, f, surpass_nan, sse_out, static_cast<hipStream_t>(stream)));
   return 0;
 }

@@ -182,7 +182,11 @@ int cumf_unpack_upper(const float* packed, float* full, long batch, int f, void*
 /*
  * Sum of squared errors over `count` ratings (RMSE kernel + cublasSasum,
  * als.cu:191-219, 979-991, 1006-1019): sse_out is one DEVICE double.
- * surpass_nan reproduces `#define SURPASS_NAN` (als.cu:201-211).
+ * surpass_nan reproduces `#define SURPASS_NAN` (als.cu:201-211).  *sse_out is OVERWRITTEN, not added to; count = 0
+ * writes 0.  f must be even (the factor rows are gathered in 8-byte pairs) and >= 0: f = 0 is the sum of val^2, for
+ * which row and col are still read and must hold `count` entries.  Refused with hipErrorInvalidValue and one line on
+ * stderr, before anything is launched or written: f < 0, an odd f, count < 0, a NULL sse_out, and for count > 0 a
+ * NULL val, row or col or (f > 0) a NULL table.
  */
 int cumf_sse(const float* val, const int* row, const int* col, const float* thetaT, const float* XT,
              long count, int f, int surpass_nan, double* sse_out, void* stream);
