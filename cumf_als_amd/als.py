@@ -920,11 +920,14 @@ class ALSEngine(_Engine):
 
 IMPLICIT_REG_WEIGHTED, IMPLICIT_REG_PLAIN = 0, 1
 SOLVER_CG_MATFREE = 2  # CUMF_SOLVER_CG_MATFREE: implicit feedback only
+SOLVER_BLOCK = 3  # CUMF_SOLVER_BLOCK: the iALS++ block solver, implicit feedback on one GPU only
 
 
 def _implicit_solver_id(solver) -> int:
     if solver in (SOLVER_CG_MATFREE, "cg_matfree"):
         return SOLVER_CG_MATFREE
+    if solver in (SOLVER_BLOCK, "block"):
+        return SOLVER_BLOCK
     return _solver_id(solver)
 
 
@@ -937,7 +940,7 @@ def _reg_id(reg) -> int:
 
 
 def implicit_available(f: int, solver="cg") -> bool:
-    """cumf_implicit_available: "cg" / "lu" take even 8 <= f <= 128, "cg_matfree" even 8 <= f <= 512."""
+    """cumf_implicit_available: "cg" / "lu" take even 8 <= f <= 128, "cg_matfree" and "block" even 8 <= f <= 512."""
     return bool(_libmod.load().cumf_implicit_available(int(f), _implicit_solver_id(solver)))
 
 
@@ -1016,7 +1019,8 @@ def implicit_finish(packed, G, reg_add: float, tt=None):
 def update_implicit(plan: Plan, colidx, val, gather, G, update, lambda_: float, alpha: float, reg="weighted", solver="cg",
                     cg_iters: int = 3):
     """One implicit half-iteration over the plan's rows (cumf_als_update_implicit); `update` is the CG warm start and
-    receives the solution, G is implicit_gram(gather).  solver "cg", "lu" or "cg_matfree" (the operator-only CG)."""
+    receives the solution, G is implicit_gram(gather).  solver "cg", "lu", "cg_matfree" (the operator-only CG) or "block"
+    (the iALS++ block solver, even 8 <= f <= 512: `cg_iters` counts its sweeps over the blocks of 32 features, >= 1)."""
     import torch
 
     _libmod.check(_libmod.load().cumf_als_update_implicit(
@@ -1049,7 +1053,9 @@ class ImplicitALSEngine(_Engine):
     batches.  solver "cg" (warm-started, `cg_iters` steps; rows of at most 32 entries never form their system), "lu" or
     "cg_matfree" (the same CG recurrence, no row ever forms its system); reg "weighted" (lambda n_u, the default) or
     "plain" (lambda).  "cg" and "lu" take even 8 <= f <= 128, "cg_matfree" even 8 <= f <= 512; at 128 < f <= 512
-    solver "cg" runs "cg_matfree", the only CG there ("lu" and nonnegative=True stay limited to f <= 128)."""
+    solver "cg" runs "cg_matfree", the only CG there ("lu" and nonnegative=True stay limited to f <= 128).  solver "block"
+    (even 8 <= f <= 512) is the iALS++ block solver: `cg_iters` sweeps of exact block Gauss-Seidel over blocks of 32
+    features per half-iteration -- the exact solve at f <= 32, and convergent to it for any f; it has no non-negative form."""
 
     def __init__(self, r, f: int, lambda_: float, alpha: float, solver="cg", cg_iters: int = 3, reg="weighted",
                  x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, nonnegative: bool = False):
@@ -1065,7 +1071,9 @@ class ImplicitALSEngine(_Engine):
                 solver = "cg_matfree"  # the only CG above f = 128
             if not implicit_available(f, solver):
                 raise ValueError(f"implicit ALS takes even 8 <= f <= 128 with solver cg | lu and even 8 <= f <= 512 with "
-                                 f"cg | cg_matfree (got f = {f}, {solver!r})")
+                                 f"cg | cg_matfree | block (got f = {f}, {solver!r})")
+            if _implicit_solver_id(solver) == SOLVER_BLOCK and int(cg_iters) < 1:
+                raise ValueError(f"solver 'block' takes cg_iters (its sweeps) >= 1 (got {cg_iters})")
         self.lam, self.alpha = float(lambda_), float(alpha)
         self.solver, self.cg_iters, self.reg = solver, int(cg_iters), _reg_id(reg)
         super().__init__(r, f, x_batch, theta_batch, chunk)

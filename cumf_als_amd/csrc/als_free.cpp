@@ -44,7 +44,12 @@ int cumf::plan_free_lists(cumf_plan* p, const FreeSegLists** out) {
   }
   std::vector<long long> seg_begin;
   std::vector<int> seg_row, seg_len, row_seg0(rows), row_nseg(rows);
+  long long ent_begin = 0, ent_end = 0;
   for (size_t u = 0; u < rows; ++u) {
+    if (len[u] > 0) {
+      if (ent_end == 0 || start[u] < ent_begin) ent_begin = start[u];
+      if (start[u] + len[u] > ent_end) ent_end = start[u] + len[u];
+    }
     row_seg0[u] = (int)seg_row.size();
     for (int o = 0; o < len[u]; o += kFreeSeg) {
       seg_begin.push_back(start[u] + o);
@@ -70,6 +75,8 @@ int cumf::plan_free_lists(cumf_plan* p, const FreeSegLists** out) {
     l->d_row_len = l->d_row_nseg + rows;
   }
   l->n_seg = (long)ns;
+  l->ent_begin = ent_begin;
+  l->ent_end = ent_end;
   l->built = true;
   return 0;
 }

@@ -31,7 +31,8 @@ constexpr int kFreeRegPlain = 1;  // ... and its reg mode with reg_u = lambda (C
 struct FreeSegLists {
   bool built = false;
   long n_seg = 0;
-  char* d_block = nullptr;           // the device block the arrays below point into
+  long long ent_begin = 0, ent_end = 0;  // the stored entries of the plan's rows lie in [ent_begin, ent_end) of colidx / val
+  char* d_block = nullptr;          // the device block the arrays below point into
   long long* d_seg_begin = nullptr;  // n_seg: first entry of each segment (index into colidx / val)
   int* d_seg_row = nullptr;          // ... its row
   int* d_seg_len = nullptr;          // ... its entries, at most kFreeSeg

@@ -6,6 +6,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "als_block.h"
 #include "als_implicit.h"
 #include "cumf_als_capi.h"
 #include "cumf_implicit_capi.h"
@@ -41,6 +42,7 @@ namespace {
 bool implicit_f_ok(int f) { return f >= 8 && f <= 128 && (f % 2) == 0; }
 bool solver_f_ok(int f, int solver) {
   if (solver == CUMF_SOLVER_CG_MATFREE) return matfree_f_ok(f);
+  if (solver == CUMF_SOLVER_BLOCK) return block_f_ok(f);
   return implicit_f_ok(f) && (solver == CUMF_SOLVER_CG || solver == CUMF_SOLVER_LU);
 }
 
@@ -140,15 +142,19 @@ int check_args(const char* who, const cumf_plan* p, int f, int reg_mode, int max
 //   Both then set the rows without stored entries to 0.
 //   CG_MATFREE  no system is formed: every row runs the operator-only CG of als_implicit_free.hip (sparse pass over the row's
 //       segments, row pass with G v on the matrix pipe and the CG updates), which also sets the empty rows to 0.
+//   BLOCK  no system is formed either: cg_iters sweeps of the block solver of als_block.h over every row, which sets the
+//       empty rows to 0 too.
 struct ImplicitRoute {
   bool materialise_all;  // LU
   bool matfree;          // CG_MATFREE
+  bool block;            // BLOCK
   long n_short;          // CG: items [n_items - n_short, n_items) on the Gram-free CG
 };
 ImplicitRoute implicit_route(const cumf_plan* p, int solver) {
-  if (solver == CUMF_SOLVER_LU) return ImplicitRoute{true, false, 0};
-  if (solver == CUMF_SOLVER_CG_MATFREE) return ImplicitRoute{false, true, 0};
-  return ImplicitRoute{false, false, p->n_short};
+  if (solver == CUMF_SOLVER_LU) return ImplicitRoute{true, false, false, 0};
+  if (solver == CUMF_SOLVER_CG_MATFREE) return ImplicitRoute{false, true, false, 0};
+  if (solver == CUMF_SOLVER_BLOCK) return ImplicitRoute{false, false, true, 0};
+  return ImplicitRoute{false, false, false, p->n_short};
 }
 
 // The matrix-free half-iteration: the driver of als_free.cpp on the implicit kernels, with the scratch kinds of this file.
@@ -238,7 +244,7 @@ extern "C" int cumf_implicit_finish(const float* packed, const float* G, float r
 extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx, const float* val, const float* gather,
                                         const float* G, float* update, int f, float lambda, float alpha, int reg_mode,
                                         int solver, int cg_iters, void* stream) {
-  int rc = check_args("cumf_als_update_implicit", pc, f, reg_mode, solver == CUMF_SOLVER_CG_MATFREE ? 512 : 128);
+  int rc = check_args("cumf_als_update_implicit", pc, f, reg_mode, solver == CUMF_SOLVER_CG_MATFREE || solver == CUMF_SOLVER_BLOCK ? 512 : 128);
   if (rc) return rc;
   if (!cumf_implicit_available(f, solver)) {
     fprintf(stderr, "cumf_als_update_implicit: unknown solver %d\n", solver);
@@ -251,6 +257,13 @@ extern "C" int cumf_als_update_implicit(const cumf_plan_t* pc, const int* colidx
   const ImplicitRoute r = implicit_route(p, solver);
   ScratchLease lease;
   if (r.matfree) return update_matfree(p, colidx, val, gather, G, update, lambda, alpha, reg_mode, cg_iters, s);
+  if (r.block) {
+    if (cg_iters < 1) {
+      fprintf(stderr, "cumf_als_update_implicit: CUMF_SOLVER_BLOCK needs cg_iters (its sweeps) >= 1 (got %d)\n", cg_iters);
+      return (int)hipErrorInvalidValue;
+    }
+    return update_block(p, colidx, val, gather, G, update, lambda, alpha, reg_mode, cg_iters, s);
+  }
   ImplicitArgs a = base_implicit_args(p, colidx, val, gather, G, f, lambda, alpha, reg_mode);
   a.update = update;
   a.cg_iters = cg_iters;

@@ -335,6 +335,11 @@ enum {
   kScratchFreeVec = 21,
   kScratchFreePart = 22,
   kScratchFreeWords = 23,
+  // iALS++ block solver (als_block.cpp): the prediction of each stored entry, the segment partials of a block step (H tiles | g),
+  // the step of the block solved last
+  kScratchBlockYhat = 24,
+  kScratchBlockPart = 25,
+  kScratchBlockStep = 26,
 };
 int scratch_get(hipStream_t stream, int kind, size_t bytes, void** out);
 // `count` elements of T (at least one) from the pool

@@ -80,6 +80,9 @@ class HipImplicitOps:
 def _solver_name(solver) -> str:
     names = {0: "cg", 1: "lu", 2: "cg_matfree", "CG": "cg", "LU": "lu"}
     solver = names.get(solver, solver)
+    if solver in (3, "block"):
+        raise ValueError("solver 'block' (the iALS++ block solver) runs on one GPU only: ImplicitALSEngine(solver='block'); "
+                         "DistImplicitALS takes cg | lu | cg_matfree")
     if solver not in _SOLVERS:
         raise ValueError(f"unknown solver {solver!r} (cg | lu | cg_matfree)")
     return solver

@@ -13,8 +13,8 @@
  * the default stream), 0 on success or a HIP error code after printing file/line to stderr, no CPU fallback.  Plans are
  * the cumf_plan_t of cumf_als_capi.h.  Scope: every entry point works on the calling process's GPU (several GPUs:
  * cumf_get_hermitian_implicit_partial + cumf_implicit_finish around the caller's own reduction, as
- * cumf_als_amd/dist_implicit.py does); even f with 8 <= f <= 512 for CUMF_SOLVER_CG_MATFREE, cumf_implicit_gram and
- * cumf_implicit_loss, even f with 8 <= f <= 128 for everything else; anything else is refused.
+ * cumf_als_amd/dist_implicit.py does); even f with 8 <= f <= 512 for CUMF_SOLVER_CG_MATFREE, CUMF_SOLVER_BLOCK,
+ * cumf_implicit_gram and cumf_implicit_loss, even f with 8 <= f <= 128 for everything else; anything else is refused.
  * Every result is bit-identical from run to run (fixed-order reductions, no float atomics).
  */
 #ifndef CUMF_IMPLICIT_CAPI_H_
@@ -30,9 +30,12 @@ enum { CUMF_IMPLICIT_REG_WEIGHTED = 0, CUMF_IMPLICIT_REG_PLAIN = 1 };
 
 /* The third implicit solver (after CUMF_SOLVER_CG = 0 and CUMF_SOLVER_LU = 1 of cumf_als_capi.h); implicit entry points only. */
 enum { CUMF_SOLVER_CG_MATFREE = 2 };
+/* The fourth: the iALS++ block solver (Rendle, Krichene, Zhang, Koren 2021), exact block Gauss-Seidel on each row's normal
+ * equations over blocks of 32 consecutive features; cumf_als_update_implicit only. */
+enum { CUMF_SOLVER_BLOCK = 3 };
 
 /* 1 when the implicit entry points take (f, solver): even f in [8, 128] with CUMF_SOLVER_CG or CUMF_SOLVER_LU, even f in
- * [8, 512] with CUMF_SOLVER_CG_MATFREE. */
+ * [8, 512] with CUMF_SOLVER_CG_MATFREE or CUMF_SOLVER_BLOCK. */
 int cumf_implicit_available(int f, int solver);
 
 /* G = table^T table of a rows x f fp32 table (even 8 <= f <= 512): f x f fp32, both triangles, exactly symmetric.  fp32
@@ -78,7 +81,12 @@ int cumf_implicit_finish(const float* packed, const float* G, float reg_add, flo
  *   CUMF_SOLVER_LU: every row materialised and solved by cumf_lu_solve_batched.
  *   CUMF_SOLVER_CG_MATFREE (even 8 <= f <= 512): no row forms A_u; every step evaluates A p = G p + T^T (w o T p) + reg p
  *                   over the stored entries and G.  The same recurrence, checked per row.
- * Rows without stored entries are set to 0 by all three. */
+ *   CUMF_SOLVER_BLOCK (even 8 <= f <= 512): cg_iters counts SWEEPS (>= 1).  From the warm start, yhat_e = y_e . x per stored
+ *                   entry; then, `cg_iters` times, for each block pi = [32 k, min(32 k + 32, f)) in order: solve
+ *                   A[pi, pi] d = (b - A x)[pi] exactly (fp32, unpivoted), x[pi] += d, yhat_e += y_e[pi] . d.  No early exit:
+ *                   every row does exactly cg_iters sweeps.  One sweep is the exact solve at f <= 32; for any f the sweeps
+ *                   converge linearly and monotonically to it.  A block step reads only the block's slice of each gathered row.
+ * Rows without stored entries are set to 0 by all four. */
 int cumf_als_update_implicit(const cumf_plan_t* plan, const int* colidx, const float* val, const float* gather,
                              const float* G, float* update, int f, float lambda, float alpha, int reg_mode, int solver,
                              int cg_iters, void* stream);
