@@ -24,6 +24,9 @@
   tables and residual ratings; `BiasedALSEngine` trains it, and ranks and evaluates by the biased prediction.
 * `update_matfree`, `matfree_available` (include/cumf_free_capi.h): the explicit half-iteration at any even 8 <= f <= 512 by a
   CG that never forms a row's system; `ALSEngine(solver="cg_matfree")` and `do_als(solver="cg_matfree")` train with it.
+* `update_block`, `block_available` (include/cumf_free_capi.h): the same half-iteration by exact block Gauss-Seidel over blocks
+  of 32 features, a row of at most 2048 entries in one kernel launch; `ALSEngine(solver="block", cg_iters=sweeps)` and
+  `do_als(solver="block")` train with it.
 * `update_weighted`, `weighted_loss`, `weighted_available` (include/cumf_weighted_capi.h): the same CG with a weight on every
   stored entry and one weight w0 on everything unstored; `WeightedALSEngine` trains with it.  `weighted_gram`,
   `update_weighted_rank1`, `weighted_rank1_loss`: the same with the rank-one weight a_u c_i on the unstored entry (u, i)
@@ -77,6 +80,8 @@ def do_als(csrrow, csrcol, csrval, cscrow, csccol, cscval, coorow, coorowtest, c
     lib = _libmod.load()
     if _is_matfree(solver) and not matfree_available(f):  # solver "cg_matfree": both half-iterations as update_matfree
         raise ValueError(f"solver 'cg_matfree' takes even 8 <= f <= 512 (got f = {f})")
+    if _is_block(solver) and (not block_available(f) or int(cg_iters) < 1):
+        raise ValueError(f"solver 'block' takes even 8 <= f <= 512 and cg_iters (its sweeps) >= 1 (got f = {f}, {cg_iters})")
     if thetat_init is None:
         rng = np.random.RandomState(0)
         thetat = (0.2 * rng.random_sample((n, f))).astype(np.float32)
@@ -107,7 +112,8 @@ def do_als(csrrow, csrcol, csrval, cscrow, csccol, cscval, coorow, coorowtest, c
         lib.cumf_last_error()
         rmse = lib.cumf_doALS_ex(*args, int(m), int(n), int(f), int(nnz), int(nnz_test), float(lambda_),
                                  int(iters), int(xbatch), int(thetabatch), int(deviceid),
-                                 SOLVER_CG_MATFREE if _is_matfree(solver) else _solver_id(solver), int(cg_iters),
+                                 SOLVER_CG_MATFREE if _is_matfree(solver) else SOLVER_BLOCK if _is_block(solver)
+                                 else _solver_id(solver), int(cg_iters),
                                  int(bool(fused)), int(bool(exact_test_grid)),
                                  int(bool(surpass_nan)), int(bool(quiet)), _hostptr(log, np.float32))
         err = lib.cumf_last_error()
@@ -242,6 +248,43 @@ def update_matfree(plan: Plan, colidx, val, gather, update, lambda_: float, cg_i
                                                          _dp(gather, torch.float32), _dp(update, torch.float32),
                                                          float(lambda_), int(cg_iters), _stream()),
                   "cumf_als_update_matfree")
+    return update
+
+
+BLOCK_ROUTES = {"auto": 0, "segmented": 1}  # CUMF_BLOCK_ROUTE_*
+
+
+def block_available(f: int) -> bool:
+    """cumf_block_available: the explicit block solver takes even 8 <= f <= 512."""
+    return bool(_libmod.load().cumf_block_available(int(f)))
+
+
+def _is_block(solver) -> bool:
+    # as `_is_matfree`: `_solver_id` keeps refusing it for the fused and materialising entry points
+    return isinstance(solver, str) and solver == "block"
+
+
+def update_block(plan: Plan, colidx, val, gather, update, lambda_: float, sweeps: int = 1, route="auto"):
+    """One explicit half-iteration over the plan's rows by exact block Gauss-Seidel on A x = b, A = T^T T + n lambda I, over
+    blocks of 32 features with a cached prediction per stored entry (cumf_als_update_block): warm start from `update`, every
+    live row runs exactly `sweeps` sweeps; one sweep is the exact solve at f <= 32 and the sweeps converge to it at any even
+    8 <= f <= 512.  A row of at most 2048 entries runs on one wave in one launch, longer rows on per-segment kernels; route
+    "segmented" sends every row there (the same bits).  Rows without entries get 0."""
+    import torch
+
+    if not block_available(plan.f):
+        raise ValueError(f"update_block takes even 8 <= f <= 512 (got f = {plan.f})")
+    if int(sweeps) < 1:
+        raise ValueError(f"update_block takes sweeps >= 1 (got {sweeps})")
+    if route not in BLOCK_ROUTES:
+        raise ValueError(f"unknown route {route!r} (auto | segmented)")
+    if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
+        raise ValueError(f"update_block: gather and update must be [rows, {plan.f}], the plan's f "
+                         f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
+    _libmod.check(_libmod.load().cumf_als_update_block(plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32),
+                                                       _dp(gather, torch.float32), _dp(update, torch.float32),
+                                                       float(lambda_), int(sweeps), BLOCK_ROUTES[route], _stream()),
+                  "cumf_als_update_block")
     return update
 
 
@@ -838,7 +881,9 @@ class ALSEngine(_Engine):
     """Explicit-feedback ALS on one GPU: the dataset of `_Engine` + the fused (or, above the tile kernels' range,
     materialising) half-iterations.  solver "cg_matfree" (even 8 <= f <= 512) runs every half-iteration as `update_matfree`,
     the same CG without any row's system: the route for f > 207, where "cg" and "lu" materialise f^2 floats per row; `fused`
-    is unused there, `nonnegative=True` with it is refused, and `update_theta_with_train_sse` is the plain update.
+    is unused there, `nonnegative=True` with it is refused, and `update_theta_with_train_sse` is the plain update.  solver
+    "block" (even 8 <= f <= 512) runs every half-iteration as `update_block` with `cg_iters` sweeps (>= 1), under the same
+    three conditions: the solver whose sweeps converge to the exact (LU) solution above f = 207.
     """
 
     def __init__(self, r, f: int, lambda_: float, solver="cg", cg_iters: int = 6, x_batch: int = 1,
@@ -854,11 +899,18 @@ class ALSEngine(_Engine):
             raise ValueError("solver 'cg_matfree' has no non-negative form (nonnegative=True runs update_nonneg, f <= 128)")
         if self.matfree and not matfree_available(f):
             raise ValueError(f"solver 'cg_matfree' takes even 8 <= f <= 512 (got f = {f})")
+        self.block = _is_block(solver)
+        self.block_route = "auto"  # "segmented": every row on the per-segment kernels (the same bits; for comparison)
+        if self.block and self.nonnegative:
+            raise ValueError("solver 'block' has no non-negative form (nonnegative=True runs update_nonneg, f <= 128)")
+        if self.block and (not block_available(f) or int(cg_iters) < 1):
+            raise ValueError(f"solver 'block' takes even 8 <= f <= 512 and cg_iters (its sweeps) >= 1 "
+                             f"(got f = {f}, cg_iters = {cg_iters})")
         if self.nonnegative:
             _check_nonneg_f(f)
             self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
         # above the tile kernels' range (f > 207) the reference's unfused data flow runs (cumf_get_hermitian + batched solver)
-        self.fused = (not self.nonnegative and not self.matfree and bool(fused)
+        self.fused = (not self.nonnegative and not self.matfree and not self.block and bool(fused)
                       and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver))))
         super().__init__(r, f, x_batch, theta_batch, chunk)
         self._tt = None
@@ -872,6 +924,8 @@ class ALSEngine(_Engine):
                 update_nonneg(p, colidx, val, gather, update, self.lam, stats=self.nnls_stats)
             elif self.matfree:
                 update_matfree(p, colidx, val, gather, update, self.lam, self.cg_iters)
+            elif self.block:
+                update_block(p, colidx, val, gather, update, self.lam, self.cg_iters, self.block_route)
             elif self.fused:
                 update_fused(p, colidx, val, gather, update, self.lam, self.solver, self.cg_iters)
             else:

@@ -1,5 +1,7 @@
-// als_block.h -- the iALS++ block solver of implicit feedback (CUMF_SOLVER_BLOCK, include/cumf_implicit_capi.h): what
-// als_block.hip (kernels) and als_block.cpp (the driver of a half-iteration) share.
+// als_block.h -- the block Gauss-Seidel solvers: the iALS++ block solver of implicit feedback (CUMF_SOLVER_BLOCK,
+// include/cumf_implicit_capi.h) and the explicit block solver (cumf_als_update_block, include/cumf_free_capi.h): what
+// als_block.hip and als_block_fused.hip (kernels; device core als_block_core.h) and als_block.cpp (the drivers of a
+// half-iteration) share.
 //
 // Exact block Gauss-Seidel on each row's normal equations A x = b (A = G + sum_e w_e t_e t_e^T + reg I, t_e the gathered factor
 // row of stored entry e).  Blocks are B = kBlockWidth consecutive features, pi_k = [B k, min(B k + B, f)).  With a cached
@@ -10,6 +12,11 @@
 //   d   = H^-1 rhs;  x[pi_k] += d;  yhat_e += t_e[pi_k] . d     (the last folded into the next step's sparse pass)
 // and touches only the block's B-float slice of each gathered row.  Every live row runs exactly `sweeps` sweeps over all
 // blocks; every sum runs in a fixed order (no float atomics), so a row's result depends on neither its neighbours nor the plan.
+//
+// Explicit feedback (als_free.h's conventions) is the same recurrence with w = 1, c_e = r_e - yhat_e and no G:
+// A = T^T T + reg I, reg = (float)n lambda, rhs = g - reg x[pi_k].  A row of at most kFreeSeg entries runs its whole
+// half-iteration on one wave in one launch (block_fused_kernel); longer rows run on the segment kernels, and both routes give
+// a row the same bits.
 #ifndef CUMF_ALS_BLOCK_H_
 #define CUMF_ALS_BLOCK_H_
 
@@ -50,6 +57,47 @@ hipError_t launch_block_open(const BlockArgs& a, hipStream_t stream);
 // block step k: the sparse pass (have_prev: first yhat += t[pi_prev] . d of the step before, prev = k - 1 or the last block)
 // and the row pass (first: rows without stored entries are zeroed)
 hipError_t launch_block_step(const BlockArgs& a, int k, int have_prev, int first, hipStream_t stream);
+
+// ---- explicit feedback
+// Entries a fused row may have, by class: LDS per workgroup of four waves is 4 x (4 224 + 4 cap) B.  The kernel's registers
+// allow five waves per SIMD (four at f > 320), that is five workgroups per CU, and cap = 960 is the largest that lets five
+// workgroups share the CU's 160 KB (5 x 32 256 B); cap = kFreeSeg leaves three.
+constexpr int kBlockClasses = 2;
+constexpr int kBlockCap[kBlockClasses] = {960, kFreeSeg};
+enum { kBlockRouteAuto = 0, kBlockRouteSegmented = 1 };  // CUMF_BLOCK_ROUTE_* of cumf_free_capi.h
+
+// The rows of a plan as the explicit block solver runs them, per route (device arrays, built on the plan at first use beside
+// its FreeSegLists and freed with it): the fused rows of each capacity class, longest first (rows without entries are of the
+// first class), and the long rows (kBlockRouteSegmented: every row) with their segments, compact.
+struct BlockRowLists {
+  bool built = false;
+  char* d_block = nullptr;
+  long n_class[kBlockClasses] = {};
+  int* d_class_rows[kBlockClasses] = {};
+  long n_lrow = 0, n_lseg = 0;
+  int* d_lrow = nullptr;        // n_lrow: the long rows
+  int* d_lrow_pseg0 = nullptr;  // ... the first segment of each in the compact segment list
+  long long* d_lseg_begin = nullptr;  // n_lseg: as FreeSegLists, the long rows' segments only
+  int* d_lseg_row = nullptr;
+  int* d_lseg_len = nullptr;
+  long long lent_begin = 0, lent_end = 0;  // the long rows' entries lie in [lent_begin, lent_end)
+  long lrow_min = 0, lrow_max = -1;        // ... and the long rows in [lrow_min, lrow_max]
+};
+struct BlockRowPlan {
+  BlockRowLists route[2];
+};
+
+// rows[0 .. nrows) of at most `cap` entries each, one wave per row: the whole half-iteration (als_block_fused.hip); a's lists
+// are the plan's FreeSegLists
+hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, hipStream_t stream);
+// block step k of the rows `rows` whose segments are a's lists: block_sparse_kernel<32, kFreeWeightNone> and the Gram-free row
+// pass block_row_free_kernel (pseg0: first partial of each row)
+hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
+                                      int have_prev, int first, hipStream_t stream);
+// One explicit block-solver half-iteration on the plan's rows (als_block.cpp): at most kBlockClasses fused launches, and
+// 1 + 2 sweeps ceil(f / B) launches over the long rows where the plan has any.  The caller holds the ScratchLease.
+CUMF_LOCAL int update_block_explicit(cumf_plan* p, const int* colidx, const float* val, const float* gather, float* update,
+                                     float lambda, int sweeps, int route, hipStream_t stream);
 
 // One block-solver half-iteration on the plan's rows (als_block.cpp): 1 + 2 sweeps ceil(f / B) launches on `stream`.
 CUMF_LOCAL int update_block(cumf_plan* p, const int* colidx, const float* val, const float* gather, const float* G,

@@ -1,5 +1,7 @@
 // als_block.hip -- the kernels of the iALS++ block solver of implicit feedback (als_block.h; CUMF_SOLVER_BLOCK), on the plan's
-// segment lists (als_free.h: one wave per segment of at most kFreeSeg entries, so rows of any length work).
+// segment lists (als_free.h: one wave per segment of at most kFreeSeg entries, so rows of any length work), and the explicit
+// block solver's route for rows longer than one segment: block_sparse_kernel at kFreeWeightNone and block_row_free_kernel, the
+// row pass without the Gram term.  The device functions they share with the fused kernel are als_block_core.h.
 //   block_open_kernel    one wave per segment: yhat_e = t_e . x (lane l holds features l + 64 q; the transposing wave reduction
 //                        of als_device.h);
 //   block_sparse_kernel  one wave per segment and block step: the block's 128-byte slice of each gathered row lands directly in
@@ -16,27 +18,13 @@
 // Every sum runs in a fixed order.  No float atomics.
 #include <hip/hip_runtime.h>
 
-#include "als_block.h"
-#include "als_free_core.h"
+#include "als_block_core.h"
 
 namespace cumf {
-
-// the sum over the 16 lanes of each DPP row, in every lane of the row
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_term<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_term<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v += dpp_term<0x141, 0xf>(v);  // row_half_mirror
-  v += dpp_term<0x140, 0xf>(v);  // row_mirror
-  return v;
-}
-__device__ __forceinline__ float read_lane(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
 
 // ---- the opening pass: yhat_e = t_e . x, the T v half of free_sparse_pass
 template <int Q>
 __global__ __launch_bounds__(kFreeThreads) void block_open_kernel(const BlockArgs a) {
-  constexpr int N = Q <= 4 ? 16 : 8;  // entries per transposing reduction
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int f = a.f;
@@ -47,44 +35,21 @@ __global__ __launch_bounds__(kFreeThreads) void block_open_kernel(const BlockArg
     float v[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) v[q] = lane + 64 * q < f ? a.x[(size_t)row * f + lane + 64 * q] : 0.f;
-    for (int s = 0; s < len; s += 64) {
-      const int cnt64 = len - s < 64 ? len - s : 64;
-      const int jl = lane < cnt64 ? a.colidx[begin + s + lane] : 0;
-      for (int b = 0; b < cnt64; b += N) {
-        const int cnt = cnt64 - b < N ? cnt64 - b : N;  // uniform
-        float P[N];
-        static_for<N>([&](auto rc) {
-          constexpr int r = decltype(rc)::value;
-          float d = 0.f;
-          if (r < cnt) {
-            const float* y = a.gather + (size_t)__builtin_amdgcn_readlane(jl, b + r) * f;
-            d = (lane < f ? y[lane] : 0.f) * v[0];
-#pragma unroll
-            for (int q = 1; q < Q; ++q) d = fmaf(lane + 64 * q < f ? y[lane + 64 * q] : 0.f, v[q], d);
-          }
-          P[r] = d;
-        });
-        const float u = reduce_transposed<N>(P, lane);  // lane L: entry b + (L mod N)
-        if (lane < cnt) a.yhat[begin + s + b + lane - a.ent0] = u;
-      }
-    }
+    block_open_pass<Q>(a, begin, len, v, lane, [&](int off, float u) { a.yhat[begin + off - a.ent0] = u; });
   }
 }
 
 // ---- the block sparse pass of step k.  have_prev: yhat is one block step behind x; the step d of block prev (k - 1, or the
-// last block when k = 0) is added first and yhat stored.
+// last block when k = 0) is added first and yhat stored.  kFreeWeightAlpha: the implicit model's confidence weights;
+// kFreeWeightNone: the explicit model, w = 1 and c_e = r_e - yhat_e.
 template <int B, FreeWeight kWeight>
 __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockArgs a, int k, int have_prev) {
   static_assert(B == 32, "two 16-wide half-slices per entry");
-  static_assert(kWeight == kFreeWeightAlpha, "the explicit and weighted clients are not instantiated yet");
-  constexpr int U = 4;  // four-entry groups in flight
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = lane & 15, kap = lane >> 4;
   const int f = a.f;
-  const int c0 = B * k, p0 = B * (k > 0 ? k - 1 : (f + B - 1) / B - 1);
-  const bool v0 = c0 + i < f, v1 = c0 + 16 + i < f;  // a ragged last block reads zeros beyond f
-  const bool pv0 = p0 + i < f, pv1 = p0 + 16 + i < f;
+  const BlockCols bc = block_cols(f, k, i);
   for (long long sg = (long long)blockIdx.x * 4 + wave; sg < a.nseg; sg += (long long)gridDim.x * 4) {
     const int row = a.seg_row[sg];
     const long long begin = a.seg_begin[sg];
@@ -94,8 +59,7 @@ __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockA
       d0 = a.d[(size_t)row * B + i];
       d1 = a.d[(size_t)row * B + 16 + i];
     }
-    f32x4 H00 = {0.f, 0.f, 0.f, 0.f}, H01 = H00, H11 = H00;
-    float g0 = 0.f, g1 = 0.f;
+    BlockAcc acc = block_acc_zero();
     for (int s = 0; s < len; s += 64) {
       const int cnt64 = len - s < 64 ? len - s : 64;
       const bool live = lane < cnt64;
@@ -103,56 +67,22 @@ __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockA
       const int jl = live ? a.colidx[e] : 0;
       const float rl = live ? a.val[e] : 0.f;
       const float yl = live ? a.yhat[e - a.ent0] : 0.f;
-      const float wl = live ? a.alpha * fabsf(rl) : 0.f;       // kFreeWeightAlpha: the confidence weight
-      const float cl = (live && rl > 0.f) ? 1.f + wl : 0.f;  // ... and (1 + w) p
-      float ynew = 0.f;  // lane (kap, i) collects the new yhat of entry 4 i + kap
-      const int ngroups = (cnt64 + 3) >> 2;
-      for (int g = 0; g < ngroups; g += U) {
-        float t0[U], t1[U], q0[U], q1[U];
-        static_for<U>([&](auto uc) {
-          constexpr int u = decltype(uc)::value;
-          const int src = 4 * (g + u) + kap;
-          const bool ok = src < cnt64;
-          const float* y = a.gather + (size_t)__shfl(jl, src & 63) * f;
-          t0[u] = (ok && v0) ? y[c0 + i] : 0.f;
-          t1[u] = (ok && v1) ? y[c0 + 16 + i] : 0.f;
-          q0[u] = q1[u] = 0.f;
-          if (have_prev) {
-            q0[u] = (ok && pv0) ? y[p0 + i] : 0.f;
-            q1[u] = (ok && pv1) ? y[p0 + 16 + i] : 0.f;
-          }
-        });
-        static_for<U>([&](auto uc) {
-          constexpr int u = decltype(uc)::value;
-          if (g + u < ngroups) {  // uniform
-            const int src = (4 * (g + u) + kap) & 63;  // an entry beyond cnt64 has w = c = 0 and zero slices
-            const float w = __shfl(wl, src), c = __shfl(cl, src);
-            float y = __shfl(yl, src);
-            if (have_prev) {
-              y += row16_sum(fmaf(q1[u], d1, q0[u] * d0));
-              ynew = g + u == i ? y : ynew;
-            }
-            const float ce = fmaf(-w, y, c);
-            g0 = fmaf(t0[u], ce, g0);
-            g1 = fmaf(t1[u], ce, g1);
-            const float w0 = w * t0[u], w1 = w * t1[u];
-            H00 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0, t0[u], H00, 0, 0, 0);
-            H01 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0, t1[u], H01, 0, 0, 0);
-            H11 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1, t1[u], H11, 0, 0, 0);
-          }
-        });
+      float wl = 0.f, cl = rl;
+      if constexpr (kWeight == kFreeWeightAlpha) {
+        wl = live ? a.alpha * fabsf(rl) : 0.f;       // the confidence weight
+        cl = (live && rl > 0.f) ? 1.f + wl : 0.f;  // ... and (1 + w) p
       }
+      // lane (kap, i) collects the new yhat of entry 4 i + kap
+      const float ynew = block_accumulate64<kWeight>(a.gather, f, bc, cnt64, jl, wl, cl, yl, have_prev, d0, d1, i, kap, acc);
       if (have_prev && 4 * i + kap < cnt64) a.yhat[begin + s + 4 * i + kap - a.ent0] = ynew;
     }
-    // the four lane groups of g, in group order
-    g0 = ((__shfl(g0, i) + __shfl(g0, 16 + i)) + __shfl(g0, 32 + i)) + __shfl(g0, 48 + i);
-    g1 = ((__shfl(g1, i) + __shfl(g1, 16 + i)) + __shfl(g1, 32 + i)) + __shfl(g1, 48 + i);
+    const float g0 = block_g_sum(acc.g0, i), g1 = block_g_sum(acc.g1, i);
     float* out = a.part + (size_t)sg * kBlockPart;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      out[(4 * kap + r) * 16 + i] = H00[r];
-      out[256 + (4 * kap + r) * 16 + i] = H01[r];
-      out[512 + (4 * kap + r) * 16 + i] = H11[r];
+      out[(4 * kap + r) * 16 + i] = acc.H00[r];
+      out[256 + (4 * kap + r) * 16 + i] = acc.H01[r];
+      out[512 + (4 * kap + r) * 16 + i] = acc.H11[r];
     }
     if (kap == 0) out[768 + i] = g0, out[768 + 16 + i] = g1;
   }
@@ -163,7 +93,7 @@ template <int Q, int B>
 __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs a, int k, int first) {
   static_assert(B == 32, "two 16-row tiles x two 16-column tiles, one per wave; one matrix row per lane of a half wave");
   constexpr int P = 64 * Q + 4;  // LDS pitch of the staged x: the 16 rows one MFMA operand reads start 4 banks apart
-  constexpr int HP = B + 1;
+  constexpr int HP = kBlockTilePitch;
   __shared__ float vs[kFreeRows * P];
   __shared__ float gx[kFreeRows * HP];  // (G x)[rows, pi_k]
   __shared__ float gpp[B * HP];         // G[pi_k, pi_k], a ragged block padded with the identity
@@ -217,62 +147,61 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
       continue;
     }
     const float reg = a.reg_mode == kFreeRegPlain ? a.lambda : (float)n * a.lambda;
-    const int seg0 = a.row_seg0[row], ns = a.row_nseg[row];
-    float hp[12], gp = 0.f;
-#pragma unroll
-    for (int m = 0; m < 12; ++m) hp[m] = 0.f;
-    for (int sgi = 0; sgi < ns; ++sgi) {  // in segment order
-      const float* part = a.part + (size_t)(seg0 + sgi) * kBlockPart;
-#pragma unroll
-      for (int m = 0; m < 12; ++m) hp[m] += part[lane + 64 * m];
-      if (lane < B) gp += part[768 + lane];
-    }
     // the tiles into the wave's H: the upper triangles of H00 and H11 and all of H01, mirrored
-#pragma unroll
-    for (int m = 0; m < 12; ++m) {
-      const int t = m >> 2, ri = ((lane + 64 * m) >> 4) & 15, ci = lane & 15;
-      const int R = t == 2 ? 16 + ri : ri, C = t == 0 ? ci : 16 + ci;
-      if (t == 1 || ci >= ri) {
-        Hs[R * HP + C] = (R == C && R < bw) ? hp[m] + reg : hp[m];
-        if (R != C) Hs[C * HP + R] = hp[m];
-      }
-    }
+    const float gp = block_partials_to_tile(a.part + (size_t)a.row_seg0[row] * kBlockPart, a.row_nseg[row], Hs, lane, reg, bw);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
     float hrow[B];
 #pragma unroll
     for (int j = 0; j < B; ++j) hrow[j] = Hs[i * HP + j] + gpp[i * HP + j];
     const float xv = i < bw ? vs[rr * P + c0 + i] : 0.f;
-    float rhs = i < bw ? (gp - gx[rr * HP + i]) - reg * xv : 0.f;
+    const float rhs = i < bw ? (gp - gx[rr * HP + i]) - reg * xv : 0.f;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();  // Hs is free for the wave's next row
-    float rd = 0.f;  // lane p: 1 / u_pp
-    // elimination without pivoting (H is symmetric positive definite): lane i holds row i; pivot row p goes round by readlane
-    static_for<B>([&](auto pc) {
-      constexpr int p = decltype(pc)::value;
-      asm volatile("" : "+v"(i));  // the lane masks of each pivot are compared where they are used, not kept in SGPRs
-      const float rinv = 1.f / read_lane(hrow[p], p);
-      rd = i == p ? rinv : rd;
-      const float l = i > p ? hrow[p] * rinv : 0.f;
-      static_for<B>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        if constexpr (j > p) hrow[j] = fmaf(-l, read_lane(hrow[j], p), hrow[j]);
-        if constexpr (j > p && (j & 7) == 7) __builtin_amdgcn_sched_barrier(0);  // at most eight pivot-row values in SGPRs
-      });
-      rhs = fmaf(-l, read_lane(rhs, p), rhs);
-    });
-    float dv = 0.f;
-    static_for<B>([&](auto pc) {
-      constexpr int p = B - 1 - decltype(pc)::value;
-      asm volatile("" : "+v"(i));
-      const float xp = read_lane(rhs * rd, p);
-      dv = i == p ? xp : dv;
-      rhs = i < p ? fmaf(-hrow[p], xp, rhs) : rhs;
-    });
+    const float dv = block_solve32(hrow, rhs, i);
     if (lane < B) {
       if (lane < bw) a.x[(size_t)row * f + c0 + lane] = xv + dv;
       a.d[(size_t)row * B + lane] = dv;
     }
+  }
+}
+
+// ---- the row pass of the explicit model, whose A = T^T T + reg I has no Gram term: rhs = g - reg x[pi_k], nothing is staged
+// and no row needs another, so one wave takes one row of the list `rows` (its partials start at partial pseg0[.]).
+template <int B>
+__global__ __launch_bounds__(kFreeThreads) void block_row_free_kernel(const BlockArgs a, const int* rows, const int* pseg0,
+                                                                      long long nrows, int k, int first) {
+  constexpr int HP = kBlockTilePitch;
+  __shared__ float hs[4][B * HP];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long idx = (long long)blockIdx.x * 4 + wave;
+  if (idx >= nrows) return;  // uniform; the kernel has no workgroup barrier
+  const int f = a.f;
+  const int c0 = B * k, bw = f - c0 < B ? f - c0 : B;
+  float* Hs = hs[wave];
+  int i = lane & 31;
+  const long long row = rows[idx];
+  const int n = a.row_len[row];
+  if (n == 0) {  // uniform
+    if (first) {
+      if (lane < bw) a.x[(size_t)row * f + c0 + lane] = 0.f;
+      if (lane < B) a.d[(size_t)row * B + lane] = 0.f;
+    }
+    return;
+  }
+  const float reg = (float)n * a.lambda;
+  const float gp = block_partials_to_tile(a.part + (size_t)pseg0[idx] * kBlockPart, a.row_nseg[row], Hs, lane, reg, bw);
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  float hrow[B];
+  block_tile_row<true>(Hs, i, bw, hrow);
+  const float xv = i < bw ? a.x[(size_t)row * f + c0 + i] : 0.f;
+  const float rhs = i < bw ? gp - reg * xv : 0.f;
+  const float dv = block_solve32(hrow, rhs, i);
+  if (lane < B) {
+    if (lane < bw) a.x[(size_t)row * f + c0 + lane] = xv + dv;
+    a.d[(size_t)row * B + lane] = dv;
   }
 }
 
@@ -294,6 +223,18 @@ hipError_t launch_block_step(const BlockArgs& a, int k, int have_prev, int first
     return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth>, dim3(free_grid(a.rows, kFreeRows, 1ll << 30)),
                               dim3(kFreeThreads), 0, stream, a, k, first);
   });
+}
+
+hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
+                                      int have_prev, int first, hipStream_t stream) {
+  if (nrows <= 0) return hipSuccess;
+  if (a.nseg > 0) {
+    const hipError_t e = launch_kernel(block_sparse_kernel<kBlockWidth, kFreeWeightNone>, dim3(free_grid(a.nseg, 4, 16384)),
+                                       dim3(kFreeThreads), 0, stream, a, k, have_prev);
+    if (e != hipSuccess) return e;
+  }
+  return launch_item_kernel(block_row_free_kernel<kBlockWidth>, dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), 0,
+                            stream, a, rows, pseg0, nrows, k, first);
 }
 
 }  // namespace cumf

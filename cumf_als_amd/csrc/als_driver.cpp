@@ -137,9 +137,15 @@ extern "C" float cumf_doALS_ex(const int* csrRowIndexHostPtr, const int* csrColI
   if (THETA_BATCH < 1) THETA_BATCH = 1;
   // solver 2: both half-iterations on the matrix-free CG (cumf_free_capi.h), which forms no system: neither the fused
   // kernels nor the Gram batch of the unfused path
-  const bool matfree = solver == CUMF_SOLVER_CG_MATFREE;
+  // solver 3: both on the explicit block solver (cumf_als_update_block), cg_iters its sweeps; it forms no system either
+  const bool block = solver == CUMF_SOLVER_BLOCK;
+  const bool matfree = solver == CUMF_SOLVER_CG_MATFREE || block;
   if (matfree && !cumf_matfree_available(f)) {
-    fprintf(stderr, "doALS: the matrix-free CG needs even 8 <= f <= 512 (got %d)\n", f);
+    fprintf(stderr, "doALS: the %s needs even 8 <= f <= 512 (got %d)\n", block ? "block solver" : "matrix-free CG", f);
+    DRV_CHECK(hipErrorInvalidValue);
+  }
+  if (block && cg_iters < 1) {
+    fprintf(stderr, "doALS: the block solver needs cg_iters (its sweeps) >= 1 (got %d)\n", cg_iters);
     DRV_CHECK(hipErrorInvalidValue);
   }
   if (matfree || !cumf_fused_available(f, solver)) fused = 0;
@@ -233,7 +239,11 @@ extern "C" float cumf_doALS_ex(const int* csrRowIndexHostPtr, const int* csrColI
 
   auto half_iteration = [&](Side& s, const float* gather, float* update, double* sse_bins) {
     for (int b = 0; b < s.nbatch; ++b) {
-      if (matfree) {
+      if (block) {
+        if (!quiet) printf("\tBlock solver with fp32.\n");
+        DRV_CHECK(cumf_als_update_block(s.plans[b], s.d_colidx, s.d_val, gather, update, lambda, cg_iters,
+                                        CUMF_BLOCK_ROUTE_AUTO, nullptr));
+      } else if (matfree) {
         if (!quiet) printf("\tCG solver with fp32.\n");
         DRV_CHECK(cumf_als_update_matfree(s.plans[b], s.d_colidx, s.d_val, gather, update, lambda, cg_iters, nullptr));
       } else if (fused) {
@@ -350,6 +360,7 @@ extern "C" float cumf_doALS(const int* csrRowIndexHostPtr, const int* csrColInde
   const char* s = getenv("CUMF_ALS_SOLVER");
   const int solver = (s && (strcmp(s, "lu") == 0 || strcmp(s, "LU") == 0)) ? CUMF_SOLVER_LU
                      : (s && strcmp(s, "cg_matfree") == 0)                  ? CUMF_SOLVER_CG_MATFREE
+                     : (s && strcmp(s, "block") == 0)                       ? CUMF_SOLVER_BLOCK
                                                                             : CUMF_SOLVER_CG;
   const char* pth = getenv("CUMF_ALS_PATH");
   const int fused = !(pth && strcmp(pth, "unfused") == 0);

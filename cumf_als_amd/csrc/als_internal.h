@@ -368,6 +368,10 @@ void free_implicit_lists(ImplicitLists* lists);
 // als_free.cpp).
 struct FreeSegLists;
 void free_seg_lists(FreeSegLists* lists);
+// The row classes and long-row segments of the explicit block solver, built on a plan at first use and freed with it
+// (als_block.h, als_block.cpp).
+struct BlockRowPlan;
+void free_block_rows(BlockRowPlan* lists);
 
 }  // namespace cumf
 
@@ -406,6 +410,8 @@ struct cumf_plan {
   cumf::ImplicitLists* implicit = nullptr;
   // matrix-free CG, explicit and implicit: the row segments of als_free.cpp (built on first use, freed with the plan)
   cumf::FreeSegLists* free_seg = nullptr;
+  // explicit block solver: the row classes and long-row segments of als_block.cpp (built on first use, freed with the plan)
+  cumf::BlockRowPlan* block_rows = nullptr;
 };
 
 namespace cumf {

@@ -267,6 +267,7 @@ extern "C" int cumf_plan_destroy(cumf_plan_t* p) {
   if (p->d_part) (void)hipFree(p->d_part);
   free_implicit_lists(p->implicit);
   free_seg_lists(p->free_seg);
+  free_block_rows(p->block_rows);
   delete p;
   return 0;
 }

@@ -16,9 +16,19 @@
  * the default stream), 0 on success or a HIP error code after printing the reason to stderr, no CPU fallback.  Plans are the
  * cumf_plan_t of cumf_als_capi.h; a row's result does not depend on the plan's chunks, on the batch cuts or on the other
  * rows, and every result is bit-identical from run to run (fixed-order sums, no float atomics).
- * Scope: one GPU, the unbiased unconstrained model, CG only.  cumf_doALS_ex takes solver 2 (the value of
+ * Scope: one GPU, the unbiased unconstrained model, the CG and the block solver below.  cumf_doALS_ex takes solver 2 (the value of
  * CUMF_SOLVER_CG_MATFREE in cumf_implicit_capi.h; environment CUMF_ALS_SOLVER=cg_matfree for doALS) and runs both
  * half-iterations here.  CUMF_SOLVER_CG keeps its routes at every f: cumf_fused_available(f, 2) stays 0.
+ *
+ * The block solver (cumf_als_update_block) solves the same systems by exact block Gauss-Seidel over blocks of 32 features,
+ * pi_k = [32 k, min(32 k + 32, f)), with a cached prediction per stored entry: warm start from `update`, then
+ *   yhat_e = y_e . x;   `sweeps` times, for every block k:
+ *     g = sum_e y_e[pi_k] (r_e - yhat_e),   H = sum_e y_e[pi_k] y_e[pi_k]^T + reg_u I,
+ *     d = H^-1 (g - reg_u x[pi_k]),   x[pi_k] += d,   yhat_e += y_e[pi_k] . d.
+ * Every live row runs exactly `sweeps` sweeps; one sweep is the exact solve at f <= 32 and the sweeps converge to it at any f.
+ * A row of at most 2048 stored entries runs its whole half-iteration on one wave in one kernel launch; longer rows run on
+ * per-segment kernels.  CUMF_BLOCK_ROUTE_SEGMENTED sends every row that way: the same bits, for comparison.  cumf_doALS_ex
+ * takes solver 3 (the value of CUMF_SOLVER_BLOCK; CUMF_ALS_SOLVER=block for doALS) with cg_iters as the sweep count.
  */
 #ifndef CUMF_FREE_CAPI_H_
 #define CUMF_FREE_CAPI_H_
@@ -37,6 +47,18 @@ int cumf_matfree_available(int f);
  * hipErrorInvalidValue: a NULL plan or pointer, a plan whose f is odd, below 8 or above 512. */
 int cumf_als_update_matfree(cumf_plan_t* plan, const int* colidx, const float* val, const float* gather, float* update,
                             float lambda, int cg_iters, void* stream);
+
+#define CUMF_BLOCK_ROUTE_AUTO 0
+#define CUMF_BLOCK_ROUTE_SEGMENTED 1
+
+/* 1 for even 8 <= f <= 512, else 0.  Host only: touches no device. */
+int cumf_block_available(int f);
+
+/* One block-solver half-iteration over the plan's rows at f = the plan's f; update (rows x f) is the warm start and receives
+ * the solution.  The segment lists and row classes are built on the plan at its first call here.  Refused with
+ * hipErrorInvalidValue: what cumf_als_update_matfree refuses, sweeps < 1, a route other than the two above. */
+int cumf_als_update_block(cumf_plan_t* plan, const int* colidx, const float* val, const float* gather, float* update,
+                          float lambda, int sweeps, int route, void* stream);
 
 #ifdef __cplusplus
 }
