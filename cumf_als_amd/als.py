@@ -26,7 +26,8 @@
   CG that never forms a row's system; `ALSEngine(solver="cg_matfree")` and `do_als(solver="cg_matfree")` train with it.
 * `update_block`, `block_available` (include/cumf_free_capi.h): the same half-iteration by exact block Gauss-Seidel over blocks
   of 32 features, a row of at most 2048 entries in one kernel launch; `ALSEngine(solver="block", cg_iters=sweeps)` and
-  `do_als(solver="block")` train with it.
+  `do_als(solver="block")` train with it.  `update_block_nonneg` is the same under x >= 0, each block step a 32-wide NNLS by
+  block principal pivoting on one wave: `ALSEngine(solver="block_nonneg", cg_iters=sweeps)`, non-negative ALS up to f = 512.
 * `update_weighted`, `weighted_loss`, `weighted_available` (include/cumf_weighted_capi.h): the same CG with a weight on every
   stored entry and one weight w0 on everything unstored; `WeightedALSEngine` trains with it.  `weighted_gram`,
   `update_weighted_rank1`, `weighted_rank1_loss`: the same with the rank-one weight a_u c_i on the unstored entry (u, i)
@@ -285,6 +286,35 @@ def update_block(plan: Plan, colidx, val, gather, update, lambda_: float, sweeps
                                                        _dp(gather, torch.float32), _dp(update, torch.float32),
                                                        float(lambda_), int(sweeps), BLOCK_ROUTES[route], _stream()),
                   "cumf_als_update_block")
+    return update
+
+
+def _is_block_nonneg(solver) -> bool:
+    # as `_is_block`: refused by `_solver_id`, so by every entry point and engine but ALSEngine
+    return isinstance(solver, str) and solver == "block_nonneg"
+
+
+def update_block_nonneg(plan: Plan, colidx, val, gather, update, lambda_: float, sweeps: int = 1, route="auto", stats=None):
+    """`update_block` under x >= 0 (cumf_als_update_block_nonneg): every block step is the 32-wide non-negative least-squares
+    problem z = argmin_{z >= 0} 1/2 z^T H z - c^T z, c = (g - reg x[pi]) + H x[pi], solved on one wave by block principal
+    pivoting from the passive set {x[pi] > 0}; x[pi] = z.  Block coordinate descent on the row's NNLS problem: the sweeps
+    converge to its solution, one sweep is that solution at f <= 32, at any even 8 <= f <= 512 with nothing materialised.  The
+    warm start is used as it is; after a full sweep every coordinate is >= 0.  stats: an optional int64 tensor [2] that is
+    ADDED to: (block steps not converged, 32 x 32 eliminations)."""
+    import torch
+
+    if not block_available(plan.f):
+        raise ValueError(f"update_block_nonneg takes even 8 <= f <= 512 (got f = {plan.f})")
+    if int(sweeps) < 1:
+        raise ValueError(f"update_block_nonneg takes sweeps >= 1 (got {sweeps})")
+    if route not in BLOCK_ROUTES:
+        raise ValueError(f"unknown route {route!r} (auto | segmented)")
+    if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
+        raise ValueError(f"update_block_nonneg: gather and update must be [rows, {plan.f}], the plan's f "
+                         f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
+    _libmod.check(_libmod.load().cumf_als_update_block_nonneg(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(gather, torch.float32), _dp(update, torch.float32),
+        float(lambda_), int(sweeps), BLOCK_ROUTES[route], _nnls_stats(stats), _stream()), "cumf_als_update_block_nonneg")
     return update
 
 
@@ -883,7 +913,9 @@ class ALSEngine(_Engine):
     the same CG without any row's system: the route for f > 207, where "cg" and "lu" materialise f^2 floats per row; `fused`
     is unused there, `nonnegative=True` with it is refused, and `update_theta_with_train_sse` is the plain update.  solver
     "block" (even 8 <= f <= 512) runs every half-iteration as `update_block` with `cg_iters` sweeps (>= 1), under the same
-    three conditions: the solver whose sweeps converge to the exact (LU) solution above f = 207.
+    three conditions: the solver whose sweeps converge to the exact (LU) solution above f = 207.  solver "block_nonneg" is
+    the same with every factor >= 0 (`update_block_nonneg`; statistics in `nnls_stats`): the non-negative model above
+    f = 128, where `nonnegative=True` (the materialising `update_nonneg`) ends; the two together are refused.
     """
 
     def __init__(self, r, f: int, lambda_: float, solver="cg", cg_iters: int = 6, x_batch: int = 1,
@@ -901,16 +933,22 @@ class ALSEngine(_Engine):
             raise ValueError(f"solver 'cg_matfree' takes even 8 <= f <= 512 (got f = {f})")
         self.block = _is_block(solver)
         self.block_route = "auto"  # "segmented": every row on the per-segment kernels (the same bits; for comparison)
+        self.block_nonneg = _is_block_nonneg(solver)
         if self.block and self.nonnegative:
-            raise ValueError("solver 'block' has no non-negative form (nonnegative=True runs update_nonneg, f <= 128)")
-        if self.block and (not block_available(f) or int(cg_iters) < 1):
-            raise ValueError(f"solver 'block' takes even 8 <= f <= 512 and cg_iters (its sweeps) >= 1 "
+            raise ValueError("solver 'block' has no non-negative form (nonnegative=True runs update_nonneg, f <= 128): "
+                             "the non-negative block solver is solver='block_nonneg'")
+        if self.block_nonneg and self.nonnegative:
+            raise ValueError("solver 'block_nonneg' is non-negative by itself; nonnegative=True runs update_nonneg (f <= 128): "
+                             "pass one of them")
+        if (self.block or self.block_nonneg) and (not block_available(f) or int(cg_iters) < 1):
+            raise ValueError(f"solver {solver!r} takes even 8 <= f <= 512 and cg_iters (its sweeps) >= 1 "
                              f"(got f = {f}, cg_iters = {cg_iters})")
         if self.nonnegative:
             _check_nonneg_f(f)
+        if self.nonnegative or self.block_nonneg:
             self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
         # above the tile kernels' range (f > 207) the reference's unfused data flow runs (cumf_get_hermitian + batched solver)
-        self.fused = (not self.nonnegative and not self.matfree and not self.block and bool(fused)
+        self.fused = (not self.nonnegative and not self.matfree and not self.block and not self.block_nonneg and bool(fused)
                       and bool(_libmod.load().cumf_fused_available(int(f), _solver_id(solver))))
         super().__init__(r, f, x_batch, theta_batch, chunk)
         self._tt = None
@@ -926,6 +964,9 @@ class ALSEngine(_Engine):
                 update_matfree(p, colidx, val, gather, update, self.lam, self.cg_iters)
             elif self.block:
                 update_block(p, colidx, val, gather, update, self.lam, self.cg_iters, self.block_route)
+            elif self.block_nonneg:
+                update_block_nonneg(p, colidx, val, gather, update, self.lam, self.cg_iters, self.block_route,
+                                    stats=self.nnls_stats)
             elif self.fused:
                 update_fused(p, colidx, val, gather, update, self.lam, self.solver, self.cg_iters)
             else:

@@ -136,7 +136,7 @@ static int plan_block_rows(cumf_plan* p, const FreeSegLists* fl, int route, cons
 }
 
 int cumf::update_block_explicit(cumf_plan* p, const int* colidx, const float* val, const float* gather, float* update,
-                                float lambda, int sweeps, int route, hipStream_t s) {
+                                float lambda, int sweeps, int route, bool nonneg, long long* stats, hipStream_t s) {
   static_assert(kBlockClasses == 2, "plan_block_rows packs two class lists");
   const FreeSegLists* fl = nullptr;
   int rc = plan_free_lists(p, &fl);
@@ -180,33 +180,46 @@ int cumf::update_block_explicit(cumf_plan* p, const int* colidx, const float* va
     CUMF_HIP_CHECK(launch_block_open(b, s));
     for (int sweep = 0; sweep < sweeps; ++sweep)
       for (int k = 0; k < nb; ++k)
-        CUMF_HIP_CHECK(launch_block_step_explicit(b, l->d_lrow, l->d_lrow_pseg0, l->n_lrow, k, sweep > 0 || k > 0, sweep == 0, s));
+        CUMF_HIP_CHECK(launch_block_step_explicit(b, l->d_lrow, l->d_lrow_pseg0, l->n_lrow, k, sweep > 0 || k > 0, sweep == 0, nonneg,
+                                                 stats, s));
   }
   for (int c = kBlockClasses - 1; c >= 0; --c)
-    CUMF_HIP_CHECK(launch_block_fused(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, s));
+    CUMF_HIP_CHECK(launch_block_fused(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, nonneg, stats, s));
   return 0;
 }
 
 extern "C" int cumf_block_available(int f) { return block_f_ok(f); }
 
-extern "C" int cumf_als_update_block(cumf_plan_t* p, const int* colidx, const float* val, const float* gather, float* update,
-                                     float lambda, int sweeps, int route, void* stream) {
+// the two explicit entry points: one set of refusals
+static int block_entry(const char* who, cumf_plan_t* p, const int* colidx, const float* val, const float* gather, float* update,
+                       float lambda, int sweeps, int route, bool nonneg, long long* stats, void* stream) {
   if (!p || !colidx || !val || !gather || !update) {
-    fprintf(stderr, "cumf_als_update_block: plan, colidx, val, gather and update must not be NULL\n");
+    fprintf(stderr, "%s: plan, colidx, val, gather and update must not be NULL\n", who);
     return (int)hipErrorInvalidValue;
   }
   if (!block_f_ok(p->f)) {
-    fprintf(stderr, "cumf_als_update_block: needs a plan of even 8 <= f <= 512 (got %d)\n", p->f);
+    fprintf(stderr, "%s: needs a plan of even 8 <= f <= 512 (got %d)\n", who, p->f);
     return (int)hipErrorInvalidValue;
   }
   if (sweeps < 1) {
-    fprintf(stderr, "cumf_als_update_block: needs sweeps >= 1 (got %d)\n", sweeps);
+    fprintf(stderr, "%s: needs sweeps >= 1 (got %d)\n", who, sweeps);
     return (int)hipErrorInvalidValue;
   }
   if (route != CUMF_BLOCK_ROUTE_AUTO && route != CUMF_BLOCK_ROUTE_SEGMENTED) {
-    fprintf(stderr, "cumf_als_update_block: unknown route %d (CUMF_BLOCK_ROUTE_AUTO | CUMF_BLOCK_ROUTE_SEGMENTED)\n", route);
+    fprintf(stderr, "%s: unknown route %d (CUMF_BLOCK_ROUTE_AUTO | CUMF_BLOCK_ROUTE_SEGMENTED)\n", who, route);
     return (int)hipErrorInvalidValue;
   }
   ScratchLease lease;
-  return update_block_explicit(p, colidx, val, gather, update, lambda, sweeps, route, static_cast<hipStream_t>(stream));
+  return update_block_explicit(p, colidx, val, gather, update, lambda, sweeps, route, nonneg, stats,
+                               static_cast<hipStream_t>(stream));
+}
+
+extern "C" int cumf_als_update_block(cumf_plan_t* p, const int* colidx, const float* val, const float* gather, float* update,
+                                     float lambda, int sweeps, int route, void* stream) {
+  return block_entry("cumf_als_update_block", p, colidx, val, gather, update, lambda, sweeps, route, false, nullptr, stream);
+}
+
+extern "C" int cumf_als_update_block_nonneg(cumf_plan_t* p, const int* colidx, const float* val, const float* gather,
+                                            float* update, float lambda, int sweeps, int route, long long* stats, void* stream) {
+  return block_entry("cumf_als_update_block_nonneg", p, colidx, val, gather, update, lambda, sweeps, route, true, stats, stream);
 }

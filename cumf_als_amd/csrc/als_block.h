@@ -17,6 +17,11 @@
 // A = T^T T + reg I, reg = (float)n lambda, rhs = g - reg x[pi_k].  A row of at most kFreeSeg entries runs its whole
 // half-iteration on one wave in one launch (block_fused_kernel); longer rows run on the segment kernels, and both routes give
 // a row the same bits.
+//
+// The non-negative explicit solver (cumf_als_update_block_nonneg) changes the block step alone: with c = rhs + H x[pi_k],
+//   z = argmin_{z >= 0} 1/2 z^T H z - c^T z;   d = z - x[pi_k];   x[pi_k] = z
+// -- block coordinate descent on the row's strictly convex QP, which converges to the row's NNLS solution and is that solution
+// after one sweep at f <= 32.  Same kernels (template flag kNonneg), lists, classes and scratch.
 #ifndef CUMF_ALS_BLOCK_H_
 #define CUMF_ALS_BLOCK_H_
 
@@ -89,15 +94,18 @@ struct BlockRowPlan {
 
 // rows[0 .. nrows) of at most `cap` entries each, one wave per row: the whole half-iteration (als_block_fused.hip); a's lists
 // are the plan's FreeSegLists
-hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, hipStream_t stream);
+// nonneg: the block step under x >= 0 (block_nnls32, als_block_core.h); stats: NULL or device int64[2], ADDED to: (blocks not
+// converged, eliminations)
+hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, bool nonneg,
+                              long long* stats, hipStream_t stream);
 // block step k of the rows `rows` whose segments are a's lists: block_sparse_kernel<32, kFreeWeightNone> and the Gram-free row
 // pass block_row_free_kernel (pseg0: first partial of each row)
 hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
-                                      int have_prev, int first, hipStream_t stream);
+                                      int have_prev, int first, bool nonneg, long long* stats, hipStream_t stream);
 // One explicit block-solver half-iteration on the plan's rows (als_block.cpp): at most kBlockClasses fused launches, and
 // 1 + 2 sweeps ceil(f / B) launches over the long rows where the plan has any.  The caller holds the ScratchLease.
 CUMF_LOCAL int update_block_explicit(cumf_plan* p, const int* colidx, const float* val, const float* gather, float* update,
-                                     float lambda, int sweeps, int route, hipStream_t stream);
+                                     float lambda, int sweeps, int route, bool nonneg, long long* stats, hipStream_t stream);
 
 // One block-solver half-iteration on the plan's rows (als_block.cpp): 1 + 2 sweeps ceil(f / B) launches on `stream`.
 CUMF_LOCAL int update_block(cumf_plan* p, const int* colidx, const float* val, const float* gather, const float* G,

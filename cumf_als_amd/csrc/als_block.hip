@@ -168,9 +168,11 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
 
 // ---- the row pass of the explicit model, whose A = T^T T + reg I has no Gram term: rhs = g - reg x[pi_k], nothing is staged
 // and no row needs another, so one wave takes one row of the list `rows` (its partials start at partial pseg0[.]).
-template <int B>
+// kNonneg: block_nnls32 in place of the elimination, x[pi_k] = z, d = z - x[pi_k]; stats as in block_fused_kernel.
+template <int B, bool kNonneg>
 __global__ __launch_bounds__(kFreeThreads) void block_row_free_kernel(const BlockArgs a, const int* rows, const int* pseg0,
-                                                                      long long nrows, int k, int first) {
+                                                                      long long nrows, int k, int first,
+                                                                      unsigned long long* stats) {
   constexpr int HP = kBlockTilePitch;
   __shared__ float hs[4][B * HP];
   const int lane = threadIdx.x & 63;
@@ -194,14 +196,27 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_free_kernel(const Bloc
   const float gp = block_partials_to_tile(a.part + (size_t)pseg0[idx] * kBlockPart, a.row_nseg[row], Hs, lane, reg, bw);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __builtin_amdgcn_wave_barrier();
-  float hrow[B];
-  block_tile_row<true>(Hs, i, bw, hrow);
+  [[maybe_unused]] float hrow[B];
+  if constexpr (!kNonneg) block_tile_row<true>(Hs, i, bw, hrow);
   const float xv = i < bw ? a.x[(size_t)row * f + c0 + i] : 0.f;
   const float rhs = i < bw ? gp - reg * xv : 0.f;
-  const float dv = block_solve32(hrow, rhs, i);
-  if (lane < B) {
-    if (lane < bw) a.x[(size_t)row * f + c0 + lane] = xv + dv;
-    a.d[(size_t)row * B + lane] = dv;
+  if constexpr (kNonneg) {
+    unsigned n_failed = 0, n_elim = 0;
+    const float z = block_nnls32(Hs, i, bw, rhs, xv, n_failed, n_elim);
+    if (lane < B) {
+      if (lane < bw) a.x[(size_t)row * f + c0 + lane] = z;
+      a.d[(size_t)row * B + lane] = z - xv;
+    }
+    if (stats && lane == 0) {
+      if (n_failed) atomicAdd(stats, (unsigned long long)n_failed);
+      if (n_elim) atomicAdd(stats + 1, (unsigned long long)n_elim);
+    }
+  } else {
+    const float dv = block_solve32(hrow, rhs, i);
+    if (lane < B) {
+      if (lane < bw) a.x[(size_t)row * f + c0 + lane] = xv + dv;
+      a.d[(size_t)row * B + lane] = dv;
+    }
   }
 }
 
@@ -226,15 +241,16 @@ hipError_t launch_block_step(const BlockArgs& a, int k, int have_prev, int first
 }
 
 hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
-                                      int have_prev, int first, hipStream_t stream) {
+                                      int have_prev, int first, bool nonneg, long long* stats, hipStream_t stream) {
   if (nrows <= 0) return hipSuccess;
   if (a.nseg > 0) {
     const hipError_t e = launch_kernel(block_sparse_kernel<kBlockWidth, kFreeWeightNone>, dim3(free_grid(a.nseg, 4, 16384)),
                                        dim3(kFreeThreads), 0, stream, a, k, have_prev);
     if (e != hipSuccess) return e;
   }
-  return launch_item_kernel(block_row_free_kernel<kBlockWidth>, dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), 0,
-                            stream, a, rows, pseg0, nrows, k, first);
+  return launch_item_kernel(nonneg ? block_row_free_kernel<kBlockWidth, true> : block_row_free_kernel<kBlockWidth, false>,
+                            dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows, k, first,
+                            reinterpret_cast<unsigned long long*>(stats));
 }
 
 }  // namespace cumf

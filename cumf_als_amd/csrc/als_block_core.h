@@ -8,7 +8,9 @@
 //   block_tile_put      one element of the tiles into the 32 x 33 LDS tile, mirrored, reg on the live diagonal;
 //   block_partials_to_tile  the segment partials of a row summed in segment order and scattered with block_tile_put;
 //   block_solve32       the 32 x 32 system eliminated without pivoting in registers: lane i holds row i, the pivot row goes
-//                       round by v_readlane; the step d comes back in lanes 0..31, repeated in lanes 32..63.
+//                       round by v_readlane; the step d comes back in lanes 0..31, repeated in lanes 32..63;
+//   block_nnls32        the same 32 x 32 system under z >= 0 by block principal pivoting: the passive set is a 32-bit mask in
+//                       SGPRs, every step is block_solve32 on the masked system re-read from the LDS tile.
 #ifndef CUMF_ALS_BLOCK_CORE_H_
 #define CUMF_ALS_BLOCK_CORE_H_
 
@@ -212,6 +214,98 @@ __device__ __forceinline__ float block_solve32(float (&hrow)[kBlockWidth], float
     rhs = i < p ? fmaf(-hrow[p], xp, rhs) : rhs;
   });
   return dv;
+}
+
+// ---- the non-negative block step: z = argmin_{z >= 0} 1/2 z^T H z - c^T z with c = rhs + H x[pi], by block
+// principal pivoting (Kim & Park) with Murty's backup rule, the scheme of als_nnls.hip at f = 32 on one wave.  The passive
+// set F is a 32-bit mask that every ballot delivers wave-uniform, so the control flow is scalar: no LDS bookkeeping and no
+// barrier.  block_solve32 destroys its row, so every step re-reads row i from the wave's tile Hs, which therefore stays live
+// until this returns (32 conflict-free LDS reads against an elimination of some 600 VALU instructions; a register copy would
+// hold 32 more VGPRs across the solve).  Lanes 32..63 repeat lanes 0..31 throughout; only the low half of a ballot is used.
+__device__ __forceinline__ unsigned ballot32(bool p) { return (unsigned)__builtin_amdgcn_ballot_w64(p); }
+// the maximum over lanes 0..31 (= over the wave), wave-uniform; fmaxf drops NaN, the callers test finiteness by ballot
+__device__ __forceinline__ float block_max32(float v) {
+  v = fmaxf(v, dpp_term<0xB1, 0xf>(v));   // quad_perm [1,0,3,2]
+  v = fmaxf(v, dpp_term<0x4E, 0xf>(v));   // quad_perm [2,3,0,1]
+  v = fmaxf(v, dpp_term<0x141, 0xf>(v));  // row_half_mirror
+  v = fmaxf(v, dpp_term<0x140, 0xf>(v));  // row_mirror
+  return fmaxf(read_lane(v, 0), read_lane(v, 16));
+}
+constexpr int kBlockNnlsCap = 16 + 2 * kBlockWidth;  // passive-set steps per block
+
+// Lane i: rhs_i = (g - reg x[pi])_i and the warm start xv = x[pi]_i (both 0 for i >= bw); Hs: the tile, reg on the live
+// diagonal.  Returns z_i.  V = {F: z_i < -tol_x} u {G: y_i < -tol}, y = H z - c, tol = 32 2^-24 s, tol_x = tol / max_i H_ii,
+// s = max|c| + max_i H_ii max_F|z_i|.  Full exchange while |V| shrinks and three more times after, then Murty's single
+// exchange of the largest index.  A step that is not finite, or the cap, ends the block at the last finite iterate clamped
+// (none: max(x[pi], 0)) and counts in n_failed; n_elim counts the eliminations.  Padded rows of a ragged block (identity
+// diagonal, c = 0) have y = 0: they never enter V and end at 0.
+__device__ __forceinline__ float block_nnls32(const float* Hs, int& i, int bw, float rhs, float xv, unsigned& n_failed,
+                                              unsigned& n_elim) {
+  constexpr int B = kBlockWidth;
+  const float* hs = Hs + i * kBlockTilePitch;  // row i of the tile; the identity of the padded rows comes with the mask below
+  // the row is read eight elements at a time wherever it is needed: more loads in flight cost registers, not time
+  float c = rhs;
+  static_for<B>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    c = fmaf(hs[j], read_lane(xv, j), c);
+    if constexpr ((j & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+  });
+  const float max_d = block_max32(i < bw ? hs[i] : 0.f);
+  const float max_c = block_max32(fabsf(c));
+  const unsigned live = bw < B ? (1u << bw) - 1u : ~0u;
+  unsigned F = ballot32(xv > 0.f) & live;
+  float zres = fmaxf(xv, 0.f);
+  int best = B + 1, backup = 3;
+  bool done = false;
+  for (int step = 0; step < kBlockNnlsCap; ++step) {
+    const bool in_f = (F >> i) & 1u;
+    float z = 0.f, y = -c;  // an empty F needs no elimination
+    if (F != 0u) {          // uniform
+      // the masked system: rows and columns off F (the padded ones are never in F) are the identity, rhs 0 there
+      float hrow[B];
+      static_for<B>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        hrow[j] = in_f ? ((F >> j) & 1u ? hs[j] : 0.f) : (i == j ? 1.f : 0.f);
+        if constexpr ((j & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+      });
+      z = block_solve32(hrow, in_f ? c : 0.f, i);
+      z = in_f ? z : 0.f;
+      ++n_elim;
+      y = 0.f;
+      if (F != live) {  // uniform: a full F has no y
+        float hz = 0.f;
+        static_for<B>([&](auto jc) {
+          constexpr int j = decltype(jc)::value;
+          hz = fmaf(hs[j], read_lane(z, j), hz);
+          if constexpr ((j & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        });
+        y = in_f ? 0.f : hz - c;
+      }
+    }
+    const float s = max_c + max_d * block_max32(fabsf(z));
+    const float tol = 0x1p-19f * s;  // 32 2^-24 s
+    const float tol_x = max_d > 0.f ? tol / max_d : 0.f;
+    if (ballot32(!(isfinite(z) && isfinite(y))) != 0u || !isfinite(tol)) break;
+    zres = fmaxf(z, 0.f);
+    const unsigned V = ballot32(in_f ? z < -tol_x : y < -tol) & live;
+    const int nv = __popc(V);
+    if (nv == 0) {
+      done = true;
+      break;
+    }
+    unsigned E = V;  // full exchange
+    if (nv < best) {
+      best = nv;
+      backup = 3;
+    } else if (backup > 0) {
+      --backup;
+    } else {  // Murty: the largest infeasible index alone
+      E = 1u << (31 - __clz(V));
+    }
+    F ^= E;
+  }
+  n_failed += done ? 0u : 1u;
+  return zres;
 }
 
 }  // namespace cumf

@@ -17,9 +17,11 @@
 
 namespace cumf {
 
-template <int Q>
+// kNonneg: the block step is block_nnls32 on the same tile and right-hand side, x[pi_k] = z and d = z - x[pi_k]; the tile stays
+// live through it.  stats (kNonneg only, may be NULL): (blocks not converged, eliminations), summed per wave, integer atomics.
+template <int Q, bool kNonneg>
 __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockArgs a, const int* rows, long long nrows, int cap,
-                                                                   int sweeps) {
+                                                                   int sweeps, unsigned long long* stats) {
   constexpr int B = kBlockWidth, HP = kBlockTilePitch;
   extern __shared__ float lds[];
   const int lane = threadIdx.x & 63;
@@ -47,6 +49,7 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockAr
   for (int q = 0; q < Q; ++q) v[q] = lane + 64 * q < f ? xrow[lane + 64 * q] : 0.f;
   block_open_pass<Q>(a, begin, n, v, lane, [&](int off, float u) { ys[off] = u; });
   float dv = 0.f;  // lanes 0..31 and again 32..63: the step of the block solved last
+  [[maybe_unused]] unsigned n_failed = 0, n_elim = 0;
   for (int sweep = 0; sweep < sweeps; ++sweep)
     for (int k = 0; k < nb; ++k) {
       const int have_prev = sweep > 0 || k > 0;
@@ -75,8 +78,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockAr
       }
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
-      float hrow[B];
-      block_tile_row<true>(Hs, i, bw, hrow);
+      [[maybe_unused]] float hrow[B];
+      if constexpr (!kNonneg) block_tile_row<true>(Hs, i, bw, hrow);
       // x[pi_k]: register k >> 1, lanes 32 (k & 1) ..; the solve wants feature c0 + i in lane i of both halves
       float xk = 0.f;
 #pragma unroll
@@ -85,24 +88,35 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockAr
       const float xv = i < bw ? xs : 0.f;
       const float gp = i < 16 ? g0 : g1;  // g[i]: lane groups 1 and 3 hold g[16 + i16] in g1
       const float rhs = i < bw ? gp - reg * xv : 0.f;
+      [[maybe_unused]] float z = 0.f;
+      if constexpr (kNonneg) z = block_nnls32(Hs, i, bw, rhs, xv, n_failed, n_elim);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();  // Hs is free for the next block
-      dv = block_solve32(hrow, rhs, i);
+      if constexpr (kNonneg) dv = z - xv;
+      else dv = block_solve32(hrow, rhs, i);
       const bool mine = (lane >> 5) == (k & 1) && i < bw;
 #pragma unroll
-      for (int q = 0; q < Q; ++q) v[q] = (mine && q == (k >> 1)) ? v[q] + dv : v[q];
+      for (int q = 0; q < Q; ++q) v[q] = (mine && q == (k >> 1)) ? (kNonneg ? z : v[q] + dv) : v[q];
     }
 #pragma unroll
   for (int q = 0; q < Q; ++q)
     if (lane + 64 * q < f) xrow[lane + 64 * q] = v[q];
+  if constexpr (kNonneg)
+    if (stats && lane == 0) {
+      if (n_failed) atomicAdd(stats, (unsigned long long)n_failed);
+      if (n_elim) atomicAdd(stats + 1, (unsigned long long)n_elim);
+    }
 }
 
-hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, hipStream_t stream) {
+hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, bool nonneg,
+                              long long* stats, hipStream_t stream) {
   if (nrows <= 0) return hipSuccess;
   const size_t lds = 4 * (size_t)(kBlockWidth * kBlockTilePitch + cap) * sizeof(float);
+  auto* st = reinterpret_cast<unsigned long long*>(stats);
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
-    return launch_item_kernel(block_fused_kernel<decltype(qc)::value>, dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads),
-                              lds, stream, a, rows, nrows, cap, sweeps);
+    constexpr int Q = decltype(qc)::value;
+    return launch_item_kernel(nonneg ? block_fused_kernel<Q, true> : block_fused_kernel<Q, false>,
+                              dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), lds, stream, a, rows, nrows, cap, sweeps, st);
   });
 }
 

@@ -132,6 +132,7 @@ FREE_ABI = {
     "cumf_als_update_matfree": (_i, [_vp, _ip, _fp, _fp, _fp, _f, _i, _vp]),
     "cumf_block_available": (_i, [_i]),
     "cumf_als_update_block": (_i, [_vp, _ip, _fp, _fp, _fp, _f, _i, _i, _vp]),
+    "cumf_als_update_block_nonneg": (_i, [_vp, _ip, _fp, _fp, _fp, _f, _i, _i, _vp, _vp]),
 }
 # include/cumf_weighted_capi.h (weighted ALS on the matrix-free core, als_weighted.cpp)
 WEIGHTED_ABI = {

@@ -16,7 +16,7 @@
  * the default stream), 0 on success or a HIP error code after printing the reason to stderr, no CPU fallback.  Plans are the
  * cumf_plan_t of cumf_als_capi.h; a row's result does not depend on the plan's chunks, on the batch cuts or on the other
  * rows, and every result is bit-identical from run to run (fixed-order sums, no float atomics).
- * Scope: one GPU, the unbiased unconstrained model, the CG and the block solver below.  cumf_doALS_ex takes solver 2 (the value of
+ * Scope: one GPU, the unbiased model, the CG and the block solver below (the latter also under x >= 0).  cumf_doALS_ex takes solver 2 (the value of
  * CUMF_SOLVER_CG_MATFREE in cumf_implicit_capi.h; environment CUMF_ALS_SOLVER=cg_matfree for doALS) and runs both
  * half-iterations here.  CUMF_SOLVER_CG keeps its routes at every f: cumf_fused_available(f, 2) stays 0.
  *
@@ -59,6 +59,19 @@ int cumf_block_available(int f);
  * hipErrorInvalidValue: what cumf_als_update_matfree refuses, sweeps < 1, a route other than the two above. */
 int cumf_als_update_block(cumf_plan_t* plan, const int* colidx, const float* val, const float* gather, float* update,
                           float lambda, int sweeps, int route, void* stream);
+
+/* The same half-iteration under x >= 0 (Spark MLlib's `nonnegative`) at every f cumf_block_available takes: the block step
+ * becomes the 32-wide non-negative least-squares problem
+ *     c = (g - reg_u x[pi_k]) + H x[pi_k],   z = argmin_{z >= 0} 1/2 z^T H z - c^T z,   d = z - x[pi_k],   x[pi_k] = z,
+ * solved on one wave by block principal pivoting with Murty's backup rule from the passive set {x[pi_k] > 0} (the scheme of
+ * cumf_nnls_capi.h; at most 80 passive-set steps per block).  This is block coordinate descent on the row's NNLS problem: the
+ * sweeps converge to its unique solution, and one sweep is that solution at f <= 32.  The warm start is used as it is
+ * (negative entries enter yhat and c); after the first full sweep every coordinate is >= 0 exactly.  Nothing is
+ * materialised; routes, row classes, scratch and refusals are those of cumf_als_update_block, and a row's bits do not
+ * depend on the route.  stats: NULL or a DEVICE int64[2] that is ADDED to (integer atomics): [0] block steps that did not
+ * converge (not finite, or the step cap: they end at the last finite iterate clamped at 0), [1] 32 x 32 eliminations. */
+int cumf_als_update_block_nonneg(cumf_plan_t* plan, const int* colidx, const float* val, const float* gather, float* update,
+                                 float lambda, int sweeps, int route, long long* stats, void* stream);
 
 #ifdef __cplusplus
 }
