@@ -31,7 +31,8 @@
 * `update_weighted`, `weighted_loss`, `weighted_available` (include/cumf_weighted_capi.h): the same CG with a weight on every
   stored entry and one weight w0 on everything unstored; `WeightedALSEngine` trains with it.  `weighted_gram`,
   `update_weighted_rank1`, `weighted_rank1_loss`: the same with the rank-one weight a_u c_i on the unstored entry (u, i)
-  (`WeightedALSEngine(unobserved=(a, c))`; `popularity_weights` gives eALS's c).
+  (`WeightedALSEngine(unobserved=(a, c))`; `popularity_weights` gives eALS's c).  `update_weighted_block`: both forms by
+  the block solver (`WeightedALSEngine(solver="block", cg_iters=sweeps)`), a row of at most 2048 entries in one launch.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -1321,6 +1322,46 @@ def weighted_rank1_loss(rowptr, colidx, val, wgt, XT, thetaT, row_w0, col_w0, la
     return out
 
 
+def update_weighted_block(plan: Plan, colidx, val, wgt, gather, G, update, lambda_: float, w0: float = 0.0, reg="weighted",
+                          sweeps: int = 1, route="auto", unobserved=None):
+    """The weighted half-iteration of `update_weighted` / `update_weighted_rank1` by exact block Gauss-Seidel over blocks of 32
+    features with a cached prediction per stored entry (cumf_als_update_weighted_block): warm start from `update`, every live
+    row runs exactly `sweeps` sweeps; one sweep is the exact solve at f <= 32 and the sweeps converge to it at any even
+    8 <= f <= 512.  unobserved=(own_w0, gather_w0) is the rank-one form (w0 must stay 0, G = weighted_gram(gather, gather_w0));
+    otherwise G = implicit_gram(gather), read only when w0 > 0.  A row of at most 2048 entries runs on one wave in one launch,
+    longer rows on per-segment kernels; route "segmented" sends every row there (the same bits without a Gram term, the last
+    bits differ with one).  Rows without entries get 0."""
+    import torch
+
+    if not weighted_available(plan.f):
+        raise ValueError(f"update_weighted_block takes even 8 <= f <= 512 (got f = {plan.f})")
+    if int(sweeps) < 1:
+        raise ValueError(f"update_weighted_block takes sweeps >= 1 (got {sweeps})")
+    if route not in BLOCK_ROUTES:
+        raise ValueError(f"unknown route {route!r} (auto | segmented)")
+    w0 = _check_w0(w0)
+    own_w0 = gather_w0 = None
+    if unobserved is not None:
+        if w0 > 0:
+            raise ValueError(f"unobserved=(own_w0, gather_w0) replaces w0: pass one of them (got w0 = {w0})")
+        own_w0 = _check_rank1_vec("update_weighted_block: own_w0", unobserved[0], update.shape[0], update.device)
+        gather_w0 = _check_rank1_vec("update_weighted_block: gather_w0", unobserved[1], gather.shape[0], gather.device)
+    if (w0 > 0 or unobserved is not None) and G is None:
+        raise ValueError("update_weighted_block: w0 > 0 or unobserved weights need the Gram G of `gather`")
+    if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
+        raise ValueError(f"update_weighted_block: gather and update must be [rows, {plan.f}], the plan's f "
+                         f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
+    if G is not None and tuple(G.shape) != (plan.f, plan.f):
+        raise ValueError(f"update_weighted_block: G must be [{plan.f}, {plan.f}] (got {tuple(G.shape)})")
+    if wgt.shape != val.shape:
+        raise ValueError(f"update_weighted_block: wgt must be parallel to val (got {tuple(wgt.shape)}, {tuple(val.shape)})")
+    _libmod.check(_libmod.load().cumf_als_update_weighted_block(
+        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32), _dp(gather, torch.float32),
+        _dp(G, torch.float32), _dp(own_w0, torch.float32), _dp(gather_w0, torch.float32), _dp(update, torch.float32),
+        float(lambda_), w0, _reg_id(reg), int(sweeps), BLOCK_ROUTES[route], _stream()), "cumf_als_update_weighted_block")
+    return update
+
+
 def popularity_weights(r, c0: float, exponent: float = 0.5):
     """The eALS weights of the unstored entries of each column (He et al., SIGIR 2016): c_i = c0 n_i^e / sum_j n_j^e, n_i the
     stored entries of column i of `r` (a `datagen.Ratings`; its CSC counts), as a device fp32 tensor of length r.n that sums to
@@ -1341,7 +1382,9 @@ def popularity_weights(r, c0: float, exponent: float = 0.5):
 class WeightedALSEngine(_Engine):
     """Weighted ALS on one GPU: rating r_ui of `r` (a `datagen.Ratings` on the device) counts with the weight w_ui >= 0 of
     `weights` (a device tensor parallel to r.csr_data, CSR entry order), every unstored entry is a target of 0 with the weight
-    w0 >= 0.  Same shape as `ALSEngine`; every half-iteration is `update_weighted` (even 8 <= f <= 512, CG only), and with
+    w0 >= 0.  Same shape as `ALSEngine`; every half-iteration is `update_weighted` (even 8 <= f <= 512; solver "cg", the
+    default) or `update_weighted_block` (solver "block": `cg_iters` >= 1 counts its sweeps, which converge to the exact solve;
+    `block_route` as on ALSEngine), and with
     w0 > 0 it forms G = Y^T Y of the fixed side once, before its batches.  reg "weighted" (lambda n_u, the default) or "plain".
     w = 1, w0 = 0 is ALSEngine(solver="cg_matfree"); w = 1 + alpha |r| on ratings (r > 0) with w0 = 1 is
     ImplicitALSEngine(solver="cg_matfree").
@@ -1352,11 +1395,16 @@ class WeightedALSEngine(_Engine):
     for bit; `popularity_weights` gives the eALS column weights."""
 
     def __init__(self, r, weights, f: int, lambda_: float, w0: float = 0.0, reg="weighted", cg_iters: int = 6,
-                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, unobserved=None):
+                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, unobserved=None, solver="cg"):
         import torch
 
         if not weighted_available(f):
             raise ValueError(f"weighted ALS takes even 8 <= f <= 512 (got f = {f})")
+        if solver not in ("cg", "block"):
+            raise ValueError(f"unknown solver {solver!r} (cg | block)")
+        if solver == "block" and int(cg_iters) < 1:
+            raise ValueError(f"solver 'block' takes cg_iters (its sweeps) >= 1 (got {cg_iters})")
+        self.block, self.block_route = solver == "block", "auto"
         self.lam, self.w0 = float(lambda_), _check_w0(w0)
         self.reg, self.cg_iters = _reg_id(reg), int(cg_iters)
         dev = r.csr_indices.device
@@ -1406,12 +1454,20 @@ class WeightedALSEngine(_Engine):
         if own_w0 is not None:  # rank-one weights on the unstored entries
             weighted_gram(gather, gather_w0, self.G)
             for p in plans:
+                if self.block:
+                    update_weighted_block(p, colidx, val, wgt, gather, self.G, update, self.lam, 0.0, self.reg, self.cg_iters,
+                                          self.block_route, (own_w0, gather_w0))
+                    continue
                 update_weighted_rank1(p, colidx, val, wgt, gather, self.G, own_w0, gather_w0, update, self.lam, self.reg,
                                       self.cg_iters)
             return
         if self.w0 > 0:
             implicit_gram(gather, self.G)
         for p in plans:
+            if self.block:
+                update_weighted_block(p, colidx, val, wgt, gather, self.G, update, self.lam, self.w0, self.reg, self.cg_iters,
+                                      self.block_route)
+                continue
             update_weighted(p, colidx, val, wgt, gather, self.G, update, self.lam, self.w0, self.reg, self.cg_iters)
 
     def update_x(self):

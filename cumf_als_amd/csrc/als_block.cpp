@@ -9,6 +9,8 @@
 
 #include "als_block.h"
 #include "cumf_free_capi.h"
+#include "cumf_implicit_capi.h"
+#include "cumf_weighted_capi.h"
 
 using namespace cumf;
 
@@ -186,6 +188,104 @@ int cumf::update_block_explicit(cumf_plan* p, const int* colidx, const float* va
   for (int c = kBlockClasses - 1; c >= 0; --c)
     CUMF_HIP_CHECK(launch_block_fused(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, nonneg, stats, s));
   return 0;
+}
+
+// The weighted half-iteration: update_block_explicit's routing on the weighted kernels.  Without a Gram term (w0 == 0 and no
+// rank-one vectors) the fused kernel is block_fused_kernel at kFreeWeightArray and the long rows end in block_row_free_kernel;
+// with one, block_fused_gram_kernel and the scaled block_row_kernel over the long rows' list.
+int cumf::update_block_weighted(cumf_plan* p, const int* colidx, const float* val, const float* wgt, const float* gather,
+                                const float* G, const float* own_w0, const float* gather_w0, float* update, float lambda,
+                                float w0, int reg_mode, int sweeps, int route, hipStream_t s) {
+  const FreeSegLists* fl = nullptr;
+  int rc = plan_free_lists(p, &fl);
+  if (rc) return rc;
+  const long rows = p->row_end - p->row_begin;
+  if (rows <= 0) return 0;
+  const BlockRowLists* l = nullptr;
+  if ((rc = plan_block_rows(p, fl, route, &l))) return rc;
+  const int f = p->f, nb = (f + kBlockWidth - 1) / kBlockWidth;
+  const int mode = own_w0 ? kBlockWeightRank1 : w0 > 0.f ? kBlockWeightScalar : kBlockWeightPlain;
+  BlockArgs a{};
+  a.seg_row = fl->d_seg_row;
+  a.seg_begin = fl->d_seg_begin;
+  a.seg_len = fl->d_seg_len;
+  a.row_seg0 = fl->d_row_seg0;
+  a.row_nseg = fl->d_row_nseg;
+  a.row_len = fl->d_row_len;
+  a.rows = rows;
+  a.nseg = fl->n_seg;
+  a.ent0 = fl->ent_begin;
+  a.colidx = colidx;
+  a.val = val;
+  a.gather = gather;
+  a.G = G;
+  a.x = update + (size_t)p->row_begin * f;
+  a.f = f;
+  a.lambda = lambda;
+  a.reg_mode = reg_mode;
+  a.wgt = wgt;
+  a.own_w0 = own_w0 ? own_w0 + p->row_begin : nullptr;  // the kernels index rows from the plan's first, as they do x
+  a.gather_w0 = gather_w0;
+  a.w0 = w0;
+  if (l->n_lrow > 0) {  // the long rows first, as update_block_explicit runs them
+    BlockArgs b = a;
+    b.seg_row = l->d_lseg_row;
+    b.seg_begin = l->d_lseg_begin;
+    b.seg_len = l->d_lseg_len;
+    b.nseg = l->n_lseg;
+    b.ent0 = l->lent_begin;
+    float* d = nullptr;
+    if ((rc = scratch(s, kScratchBlockYhat, (size_t)(l->lent_end - l->lent_begin), &b.yhat)) ||
+        (rc = scratch(s, kScratchBlockPart, (size_t)b.nseg * kBlockPart, &b.part)) ||
+        (rc = scratch(s, kScratchBlockStep, (size_t)(l->lrow_max - l->lrow_min + 1) * kBlockWidth, &d)))
+      return rc;
+    b.d = d - (size_t)l->lrow_min * kBlockWidth;  // indexed by row
+    CUMF_HIP_CHECK(launch_block_open(b, s));
+    for (int sweep = 0; sweep < sweeps; ++sweep)
+      for (int k = 0; k < nb; ++k)
+        CUMF_HIP_CHECK(launch_block_step_weighted(b, l->d_lrow, l->d_lrow_pseg0, l->n_lrow, k, sweep > 0 || k > 0, sweep == 0, mode, s));
+  }
+  for (int c = kBlockClasses - 1; c >= 0; --c)
+    if (mode == kBlockWeightPlain)
+      CUMF_HIP_CHECK(launch_block_fused_weighted(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, s));
+    else
+      CUMF_HIP_CHECK(launch_block_fused_gram(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, mode, s));
+  return 0;
+}
+
+extern "C" int cumf_als_update_weighted_block(const cumf_plan_t* pc, const int* colidx, const float* val, const float* wgt,
+                                              const float* gather, const float* G, const float* own_w0, const float* gather_w0,
+                                              float* update, float lambda, float w0, int reg_mode, int sweeps, int route,
+                                              void* stream) {
+  const char* who = "cumf_als_update_weighted_block";
+  if (!pc || !colidx || !val || !wgt || !gather || !update) {
+    fprintf(stderr, "%s: plan, colidx, val, wgt, gather and update must not be NULL\n", who);
+    return (int)hipErrorInvalidValue;
+  }
+  if (!block_f_ok(pc->f)) {
+    fprintf(stderr, "%s: needs a plan of even 8 <= f <= 512 (got %d)\n", who, pc->f);
+    return (int)hipErrorInvalidValue;
+  }
+  if ((reg_mode != CUMF_IMPLICIT_REG_WEIGHTED && reg_mode != CUMF_IMPLICIT_REG_PLAIN) || !(w0 >= 0.f) || sweeps < 1) {
+    fprintf(stderr, "%s: needs reg_mode 0 or 1 (got %d), w0 >= 0 (got %g) and sweeps >= 1 (got %d)\n", who, reg_mode, (double)w0,
+            sweeps);
+    return (int)hipErrorInvalidValue;
+  }
+  if (route != CUMF_BLOCK_ROUTE_AUTO && route != CUMF_BLOCK_ROUTE_SEGMENTED) {
+    fprintf(stderr, "%s: unknown route %d (CUMF_BLOCK_ROUTE_AUTO | CUMF_BLOCK_ROUTE_SEGMENTED)\n", who, route);
+    return (int)hipErrorInvalidValue;
+  }
+  if (!own_w0 != !gather_w0 || (own_w0 && w0 != 0.f)) {
+    fprintf(stderr, "%s: own_w0 and gather_w0 come together, and with them w0 must be 0 (got %g)\n", who, (double)w0);
+    return (int)hipErrorInvalidValue;
+  }
+  if ((own_w0 || w0 > 0.f) && !G) {
+    fprintf(stderr, "%s: G must not be NULL when w0 > 0 or the rank-one vectors are given\n", who);
+    return (int)hipErrorInvalidValue;
+  }
+  ScratchLease lease;
+  return update_block_weighted(const_cast<cumf_plan*>(pc), colidx, val, wgt, gather, G, own_w0, gather_w0, update, lambda, w0,
+                               reg_mode, sweeps, route, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int cumf_block_available(int f) { return block_f_ok(f); }

@@ -1,7 +1,7 @@
 // als_block.h -- the block Gauss-Seidel solvers: the iALS++ block solver of implicit feedback (CUMF_SOLVER_BLOCK,
-// include/cumf_implicit_capi.h) and the explicit block solver (cumf_als_update_block, include/cumf_free_capi.h): what
-// als_block.hip and als_block_fused.hip (kernels; device core als_block_core.h) and als_block.cpp (the drivers of a
-// half-iteration) share.
+// include/cumf_implicit_capi.h), the explicit block solver (cumf_als_update_block, include/cumf_free_capi.h) and the weighted
+// one (cumf_als_update_weighted_block, include/cumf_weighted_capi.h): what als_block.hip, als_block_fused.hip and
+// als_block_gram.hip (kernels; device core als_block_core.h) and als_block.cpp (the drivers of a half-iteration) share.
 //
 // Exact block Gauss-Seidel on each row's normal equations A x = b (A = G + sum_e w_e t_e t_e^T + reg I, t_e the gathered factor
 // row of stored entry e).  Blocks are B = kBlockWidth consecutive features, pi_k = [B k, min(B k + B, f)).  With a cached
@@ -55,6 +55,12 @@ struct BlockArgs {
   int f;
   float lambda, alpha;
   int reg_mode;        // kFreeRegPlain: reg = lambda, else (float)n lambda
+  // the weighted clients (kFreeWeightArray / kFreeWeightRank1 of als_free_core.h; appended, so the fields above keep their
+  // kernel-argument offsets)
+  const float* wgt;        // the weight of each stored entry, indexed as val
+  const float* own_w0;     // rank-one form: the row's factor of its unstored weights, indexed as the rows of x; else NULL
+  const float* gather_w0;  // ... and the column's, indexed as the rows of `gather`
+  float w0;                // scalar form: the weight of every unstored entry
 };
 
 // yhat_e = t_e . x of every stored entry
@@ -102,6 +108,29 @@ hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nro
 // pass block_row_free_kernel (pseg0: first partial of each row)
 hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
                                       int have_prev, int first, bool nonneg, long long* stats, hipStream_t stream);
+
+// ---- weighted feedback (include/cumf_weighted_capi.h: cumf_als_update_weighted_block).  With s_u the weight of row u's
+// unstored entries (w0, or own_w0[u]) and q_e = w_e - s_u c_j the recurrence above runs on
+//   A_u = s_u G + sum_e q_e t_e t_e^T + reg I,   b_u = sum_e w_e r_e t_e:
+//   g = sum_e t_e[pi_k] (w_e r_e - q_e yhat_e),  H = sum_e q_e t t^T + s_u G[pi_k, pi_k] + reg I,
+//   rhs = (g - s_u (G x)[pi_k]) - reg x[pi_k].
+// q_e may be negative; H = s_u sum_unstored + sum_stored w + reg I stays positive definite.  BlockWeightMode: where s_u and
+// q_e come from; kBlockWeightPlain is the call without any Gram term (w0 == 0, no rank-one vectors: q_e = w_e).
+enum BlockWeightMode { kBlockWeightPlain = 0, kBlockWeightScalar = 1, kBlockWeightRank1 = 2 };
+// rows[0 .. nrows) of at most `cap` entries, one wave per row, kBlockWeightPlain: block_fused_kernel at kFreeWeightArray
+hipError_t launch_block_fused_weighted(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps,
+                                       hipStream_t stream);
+// ... with the Gram term (als_block_gram.hip: block_fused_gram_kernel); a.G is required
+hipError_t launch_block_fused_gram(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, int mode,
+                                   hipStream_t stream);
+// block step k of the rows `rows` on a's segment lists: block_sparse_kernel at the mode's weights, then block_row_free_kernel
+// (kBlockWeightPlain) or the Gram row pass block_row_kernel with the row's scale, 32 listed rows per workgroup
+hipError_t launch_block_step_weighted(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
+                                      int have_prev, int first, int mode, hipStream_t stream);
+// One weighted block-solver half-iteration on the plan's rows (als_block.cpp), routed as update_block_explicit routes.
+CUMF_LOCAL int update_block_weighted(cumf_plan* p, const int* colidx, const float* val, const float* wgt, const float* gather,
+                                     const float* G, const float* own_w0, const float* gather_w0, float* update, float lambda,
+                                     float w0, int reg_mode, int sweeps, int route, hipStream_t stream);
 // One explicit block-solver half-iteration on the plan's rows (als_block.cpp): at most kBlockClasses fused launches, and
 // 1 + 2 sweeps ceil(f / B) launches over the long rows where the plan has any.  The caller holds the ScratchLease.
 CUMF_LOCAL int update_block_explicit(cumf_plan* p, const int* colidx, const float* val, const float* gather, float* update,

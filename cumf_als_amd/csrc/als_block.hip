@@ -1,7 +1,8 @@
 // als_block.hip -- the kernels of the iALS++ block solver of implicit feedback (als_block.h; CUMF_SOLVER_BLOCK), on the plan's
 // segment lists (als_free.h: one wave per segment of at most kFreeSeg entries, so rows of any length work), and the explicit
 // block solver's route for rows longer than one segment: block_sparse_kernel at kFreeWeightNone and block_row_free_kernel, the
-// row pass without the Gram term.  The device functions they share with the fused kernel are als_block_core.h.
+// row pass without the Gram term; and the weighted block solver's (kFreeWeightArray / kFreeWeightRank1; the row pass with the
+// row's scale on the Gram term, over a row list).  The device functions they share with the fused kernels are als_block_core.h.
 //   block_open_kernel    one wave per segment: yhat_e = t_e . x (lane l holds features l + 64 q; the transposing wave reduction
 //                        of als_device.h);
 //   block_sparse_kernel  one wave per segment and block step: the block's 128-byte slice of each gathered row lands directly in
@@ -59,6 +60,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockA
       d0 = a.d[(size_t)row * B + i];
       d1 = a.d[(size_t)row * B + 16 + i];
     }
+    [[maybe_unused]] float aw = 0.f;  // kFreeWeightRank1: the row's factor of its unstored weights (uniform)
+    if constexpr (kWeight == kFreeWeightRank1) aw = a.own_w0[row];
     BlockAcc acc = block_acc_zero();
     for (int s = 0; s < len; s += 64) {
       const int cnt64 = len - s < 64 ? len - s : 64;
@@ -67,11 +70,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockA
       const int jl = live ? a.colidx[e] : 0;
       const float rl = live ? a.val[e] : 0.f;
       const float yl = live ? a.yhat[e - a.ent0] : 0.f;
-      float wl = 0.f, cl = rl;
-      if constexpr (kWeight == kFreeWeightAlpha) {
-        wl = live ? a.alpha * fabsf(rl) : 0.f;       // the confidence weight
-        cl = (live && rl > 0.f) ? 1.f + wl : 0.f;  // ... and (1 + w) p
-      }
+      float wl, cl;
+      block_entry_weight<kWeight>(a, e, live, jl, rl, aw, wl, cl);
       // lane (kap, i) collects the new yhat of entry 4 i + kap
       const float ynew = block_accumulate64<kWeight>(a.gather, f, bc, cnt64, jl, wl, cl, yl, have_prev, d0, d1, i, kap, acc);
       if (have_prev && 4 * i + kap < cnt64) a.yhat[begin + s + 4 * i + kap - a.ent0] = ynew;
@@ -89,8 +89,14 @@ __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockA
 }
 
 // ---- the block row pass of step k.  first: rows without stored entries get 0 in the block's slice of x and in d.
-template <int Q, int B>
-__global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs a, int k, int first) {
+// rows: NULL for the rows [0, nrows) with their partials at row_seg0, or a list of nrows rows whose partials start at
+// pseg0[.] (the long rows of a BlockRowLists).  kScaled (the weighted clients): the Gram term of row u is s_u G, s_u =
+// own_w0[u] where that is given, else w0 -- gx and the live part of gpp are multiplied where they are used, as kScale of
+// free_gram_rows multiplies G v; the identity that pads a ragged block is not scaled.  Without kScaled the expressions are
+// the implicit model's own.
+template <int Q, int B, bool kScaled>
+__global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs a, const int* rows, const int* pseg0,
+                                                                 long long nrows, int k, int first) {
   static_assert(B == 32, "two 16-row tiles x two 16-column tiles, one per wave; one matrix row per lane of a half wave");
   constexpr int P = 64 * Q + 4;  // LDS pitch of the staged x: the 16 rows one MFMA operand reads start 4 banks apart
   constexpr int HP = kBlockTilePitch;
@@ -103,10 +109,11 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
   const int f = a.f, KP = (f + 3) & ~3;
   const int c0 = B * k, bw = f - c0 < B ? f - c0 : B;
   const long long r0 = (long long)blockIdx.x * kFreeRows;
-  const int nr = (int)(a.rows - r0 < kFreeRows ? a.rows - r0 : kFreeRows);
+  const int nr = (int)(nrows - r0 < kFreeRows ? nrows - r0 : kFreeRows);
+  auto row_of = [&](int rr) -> long long { return rows ? (long long)rows[r0 + rr] : r0 + rr; };
   for (int e = threadIdx.x; e < kFreeRows * KP; e += kFreeThreads) {
     const int rr = e / KP, c = e - rr * KP;
-    vs[rr * P + c] = (rr < nr && c < f) ? a.x[(size_t)(r0 + rr) * f + c] : 0.f;
+    vs[rr * P + c] = (rr < nr && c < f) ? a.x[(size_t)row_of(rr) * f + c] : 0.f;
   }
   for (int e = threadIdx.x; e < B * B; e += kFreeThreads) {
     const int ri = e / B, ci = e - ri * B;
@@ -137,7 +144,7 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
   float* Hs = hs[wave];
   for (int rr = wave; rr < nr; rr += 4) {
     int i = lane & 31;  // the matrix row of this lane (the upper half wave repeats the lower and writes nothing)
-    const long long row = r0 + rr;
+    const long long row = row_of(rr);
     const int n = a.row_len[row];
     if (n == 0) {  // uniform
       if (first) {
@@ -148,14 +155,23 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
     }
     const float reg = a.reg_mode == kFreeRegPlain ? a.lambda : (float)n * a.lambda;
     // the tiles into the wave's H: the upper triangles of H00 and H11 and all of H01, mirrored
-    const float gp = block_partials_to_tile(a.part + (size_t)a.row_seg0[row] * kBlockPart, a.row_nseg[row], Hs, lane, reg, bw);
+    const int ps0 = rows ? pseg0[r0 + rr] : a.row_seg0[row];
+    const float gp = block_partials_to_tile(a.part + (size_t)ps0 * kBlockPart, a.row_nseg[row], Hs, lane, reg, bw);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
     float hrow[B];
-#pragma unroll
-    for (int j = 0; j < B; ++j) hrow[j] = Hs[i * HP + j] + gpp[i * HP + j];
     const float xv = i < bw ? vs[rr * P + c0 + i] : 0.f;
-    const float rhs = i < bw ? (gp - gx[rr * HP + i]) - reg * xv : 0.f;
+    float rhs;
+    if constexpr (kScaled) {
+      const float su = a.own_w0 ? a.own_w0[row] : a.w0;  // uniform
+#pragma unroll
+      for (int j = 0; j < B; ++j) hrow[j] = Hs[i * HP + j] + ((i < bw && j < bw) ? su * gpp[i * HP + j] : gpp[i * HP + j]);
+      rhs = i < bw ? (gp - su * gx[rr * HP + i]) - reg * xv : 0.f;
+    } else {
+#pragma unroll
+      for (int j = 0; j < B; ++j) hrow[j] = Hs[i * HP + j] + gpp[i * HP + j];
+      rhs = i < bw ? (gp - gx[rr * HP + i]) - reg * xv : 0.f;
+    }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();  // Hs is free for the wave's next row
     const float dv = block_solve32(hrow, rhs, i);
@@ -169,7 +185,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
 // ---- the row pass of the explicit model, whose A = T^T T + reg I has no Gram term: rhs = g - reg x[pi_k], nothing is staged
 // and no row needs another, so one wave takes one row of the list `rows` (its partials start at partial pseg0[.]).
 // kNonneg: block_nnls32 in place of the elimination, x[pi_k] = z, d = z - x[pi_k]; stats as in block_fused_kernel.
-template <int B, bool kNonneg>
+// kRegMode (the weighted client): reg follows a.reg_mode; without it reg = (float)n lambda, the explicit model's.
+template <int B, bool kNonneg, bool kRegMode = false>
 __global__ __launch_bounds__(kFreeThreads) void block_row_free_kernel(const BlockArgs a, const int* rows, const int* pseg0,
                                                                       long long nrows, int k, int first,
                                                                       unsigned long long* stats) {
@@ -192,7 +209,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_free_kernel(const Bloc
     }
     return;
   }
-  const float reg = (float)n * a.lambda;
+  float reg = (float)n * a.lambda;
+  if constexpr (kRegMode) reg = a.reg_mode == kFreeRegPlain ? a.lambda : reg;
   const float gp = block_partials_to_tile(a.part + (size_t)pseg0[idx] * kBlockPart, a.row_nseg[row], Hs, lane, reg, bw);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __builtin_amdgcn_wave_barrier();
@@ -235,8 +253,9 @@ hipError_t launch_block_step(const BlockArgs& a, int k, int have_prev, int first
     if (e != hipSuccess) return e;
   }
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
-    return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth>, dim3(free_grid(a.rows, kFreeRows, 1ll << 30)),
-                              dim3(kFreeThreads), 0, stream, a, k, first);
+    return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth, false>,
+                              dim3(free_grid(a.rows, kFreeRows, 1ll << 30)), dim3(kFreeThreads), 0, stream, a,
+                              (const int*)nullptr, (const int*)nullptr, a.rows, k, first);
   });
 }
 
@@ -251,6 +270,25 @@ hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const
   return launch_item_kernel(nonneg ? block_row_free_kernel<kBlockWidth, true> : block_row_free_kernel<kBlockWidth, false>,
                             dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows, k, first,
                             reinterpret_cast<unsigned long long*>(stats));
+}
+
+hipError_t launch_block_step_weighted(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
+                                      int have_prev, int first, int mode, hipStream_t stream) {
+  if (nrows <= 0) return hipSuccess;
+  if (a.nseg > 0) {
+    const hipError_t e = launch_kernel(mode == kBlockWeightRank1 ? block_sparse_kernel<kBlockWidth, kFreeWeightRank1>
+                                                                 : block_sparse_kernel<kBlockWidth, kFreeWeightArray>,
+                                       dim3(free_grid(a.nseg, 4, 16384)), dim3(kFreeThreads), 0, stream, a, k, have_prev);
+    if (e != hipSuccess) return e;
+  }
+  if (mode == kBlockWeightPlain)
+    return launch_item_kernel(block_row_free_kernel<kBlockWidth, false, true>, dim3(free_grid(nrows, 4, 1ll << 30)),
+                              dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows, k, first, (unsigned long long*)nullptr);
+  return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
+    return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth, true>,
+                              dim3(free_grid(nrows, kFreeRows, 1ll << 30)), dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows,
+                              k, first);
+  });
 }
 
 }  // namespace cumf

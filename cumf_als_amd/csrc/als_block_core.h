@@ -1,6 +1,8 @@
 // als_block_core.h -- the device core of the block Gauss-Seidel solvers (als_block.h): what the kernels of the segmented
-// route (als_block.hip: one wave per segment, partials and yhat in global memory) and the fused explicit kernel
-// (als_block_fused.hip: one wave per row, everything on chip) share, so that both sum the same terms in the same order.
+// route (als_block.hip: one wave per segment, partials and yhat in global memory) and the fused kernels
+// (als_block_fused.hip, als_block_gram.hip: one wave per row, everything on chip) share, so that all sum the same terms in the
+// same order.
+//   block_entry_weight  the weight and coefficient of a stored entry in each weight mode, as free_sparse_pass forms them;
 //   block_open_pass     yhat_e = t_e . x of a run of entries by the transposing wave reduction (lane l holds features l + 64 q);
 //   block_accumulate64  at most 64 entries of a block step, four at a time: lane i + 16 kappa loads the two 64-byte half-slices
 //                       of entry kappa as v_mfma_f32_16x16x4_f32 operands, folds the previous block's step into yhat (16-lane
@@ -85,6 +87,29 @@ __device__ __forceinline__ BlockCols block_cols(int f, int k, int i) {
   return BlockCols{c0, p0, c0 + i < f, c0 + 16 + i < f, p0 + i < f, p0 + 16 + i < f};
 }
 
+// The weight wl and coefficient cl of stored entry e (column jl, rating rl) in a live lane, formed as free_sparse_pass forms
+// them.  kFreeWeightAlpha: the confidence weight a.alpha |r| and (1 + w) p; kFreeWeightArray: q_e = wgt[e] - a.w0 and w_e r_e;
+// kFreeWeightRank1: q_e = fma(-aw, gather_w0[jl], wgt[e]) (aw = own_w0 of the row, wave-uniform; one 4-byte gather by the
+// column index the lane holds) and w_e r_e.  q_e may be negative.  A lane that is not live gets w = 0 and c = 0.
+template <FreeWeight kWeight>
+__device__ __forceinline__ void block_entry_weight(const BlockArgs& a, long long e, bool live, int jl, float rl, float aw,
+                                                   float& wl, float& cl) {
+  wl = 0.f, cl = rl;
+  if constexpr (kWeight == kFreeWeightAlpha) {
+    wl = live ? a.alpha * fabsf(rl) : 0.f;
+    cl = (live && rl > 0.f) ? 1.f + wl : 0.f;
+  } else if constexpr (kWeight == kFreeWeightArray) {
+    const float gl = live ? a.wgt[e] : 0.f;
+    wl = live ? gl - a.w0 : 0.f;
+    cl = gl * rl;
+  } else if constexpr (kWeight == kFreeWeightRank1) {
+    const float gl = live ? a.wgt[e] : 0.f;
+    const float cj = live ? a.gather_w0[jl] : 0.f;
+    wl = live ? fmaf(-aw, cj, gl) : 0.f;
+    cl = gl * rl;
+  }
+}
+
 // At most 64 entries (cnt64), entry l in lane l: column jl, weight wl (kFreeWeightNone: 1, not read), coefficient cl, cached
 // prediction yl.  have_prev: yhat += t[pi_prev] . d of the step before (d0 = d[i], d1 = d[16 + i]) comes first; the return
 // value is then the new yhat of entry 4 i + kappa in lane i + 16 kappa.  An entry beyond cnt64 has c = 0 and zero slices.
@@ -92,7 +117,6 @@ template <FreeWeight kWeight>
 __device__ __forceinline__ float block_accumulate64(const float* gather, int f, const BlockCols& bc, int cnt64, int jl, float wl,
                                                     float cl, float yl, int have_prev, float d0, float d1, int i, int kap,
                                                     BlockAcc& acc) {
-  static_assert(kWeight == kFreeWeightNone || kWeight == kFreeWeightAlpha, "the weighted clients are not instantiated yet");
   constexpr int U = 4;  // four-entry groups in flight
   float ynew = 0.f;
   const int ngroups = (cnt64 + 3) >> 2;

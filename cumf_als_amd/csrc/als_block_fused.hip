@@ -19,7 +19,9 @@ namespace cumf {
 
 // kNonneg: the block step is block_nnls32 on the same tile and right-hand side, x[pi_k] = z and d = z - x[pi_k]; the tile stays
 // live through it.  stats (kNonneg only, may be NULL): (blocks not converged, eliminations), summed per wave, integer atomics.
-template <int Q, bool kNonneg>
+// kWeight: kFreeWeightNone, the explicit model, or kFreeWeightArray, the weighted model without a Gram term (w0 == 0: the
+// entry's weight is one more coalesced load per 64 entries, and reg follows a.reg_mode).
+template <int Q, bool kNonneg, FreeWeight kWeight>
 __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockArgs a, const int* rows, long long nrows, int cap,
                                                                    int sweeps, unsigned long long* stats) {
   constexpr int B = kBlockWidth, HP = kBlockTilePitch;
@@ -43,7 +45,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockAr
     return;
   }
   const long long begin = a.seg_begin[a.row_seg0[row]];
-  const float reg = (float)n * a.lambda;
+  float reg = (float)n * a.lambda;
+  if constexpr (kWeight != kFreeWeightNone) reg = a.reg_mode == kFreeRegPlain ? a.lambda : reg;
   float v[Q];
 #pragma unroll
   for (int q = 0; q < Q; ++q) v[q] = lane + 64 * q < f ? xrow[lane + 64 * q] : 0.f;
@@ -65,8 +68,9 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_kernel(const BlockAr
         const int jl = live ? a.colidx[begin + s + lane] : 0;
         const float rl = live ? a.val[begin + s + lane] : 0.f;
         const float yl = live ? ys[s + lane] : 0.f;
-        const float ynew = block_accumulate64<kFreeWeightNone>(a.gather, f, bc, cnt64, jl, 0.f, rl, yl, have_prev, d0, d1, i16,
-                                                               kap, acc);
+        float wl, cl;
+        block_entry_weight<kWeight>(a, begin + s + lane, live, jl, rl, 0.f, wl, cl);
+        const float ynew = block_accumulate64<kWeight>(a.gather, f, bc, cnt64, jl, wl, cl, yl, have_prev, d0, d1, i16, kap, acc);
         if (have_prev && 4 * i16 + kap < cnt64) ys[s + 4 * i16 + kap] = ynew;
       }
       const float g0 = block_g_sum(acc.g0, i16), g1 = block_g_sum(acc.g1, i16);
@@ -115,8 +119,18 @@ hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nro
   auto* st = reinterpret_cast<unsigned long long*>(stats);
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
     constexpr int Q = decltype(qc)::value;
-    return launch_item_kernel(nonneg ? block_fused_kernel<Q, true> : block_fused_kernel<Q, false>,
+    return launch_item_kernel(nonneg ? block_fused_kernel<Q, true, kFreeWeightNone> : block_fused_kernel<Q, false, kFreeWeightNone>,
                               dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), lds, stream, a, rows, nrows, cap, sweeps, st);
+  });
+}
+
+hipError_t launch_block_fused_weighted(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps,
+                                       hipStream_t stream) {
+  if (nrows <= 0) return hipSuccess;
+  const size_t lds = 4 * (size_t)(kBlockWidth * kBlockTilePitch + cap) * sizeof(float);
+  return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
+    return launch_item_kernel(block_fused_kernel<decltype(qc)::value, false, kFreeWeightArray>, dim3(free_grid(nrows, 4, 1ll << 30)),
+                              dim3(kFreeThreads), lds, stream, a, rows, nrows, cap, sweeps, (unsigned long long*)nullptr);
   });
 }
 

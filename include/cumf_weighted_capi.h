@@ -26,8 +26,9 @@
  * the default stream), 0 on success or a HIP error code after printing the reason to stderr, no CPU fallback.  Plans are the
  * cumf_plan_t of cumf_als_capi.h; a row's result does not depend on the plan's chunks, on the batch cuts or on the other
  * rows, and every result is bit-identical from run to run (fixed-order sums, no float atomics).
- * Scope: one GPU, CG only, the unbiased unconstrained model.  Not covered: LU or any materialised weighted system, a
- * regulariser lambda sum_i w_ui, biases or non-negativity combined with weights, cumf_doALS, several GPUs.
+ * Scope: one GPU, the unbiased unconstrained model; the CG above, or the block solver at the end of this file, whose sweeps
+ * converge to the exact solve.  Not covered: LU or any materialised weighted system, a regulariser lambda sum_i w_ui, biases
+ * or non-negativity combined with weights, cumf_doALS, several GPUs.
  */
 #ifndef CUMF_WEIGHTED_CAPI_H_
 #define CUMF_WEIGHTED_CAPI_H_
@@ -92,6 +93,26 @@ int cumf_als_update_weighted_rank1(const cumf_plan_t* plan, const int* colidx, c
 int cumf_weighted_rank1_loss(const int* rowptr, const int* colidx, const float* val, const float* wgt, const float* XT,
                              const float* thetaT, const float* row_w0, const float* col_w0, long m, long n, int f,
                              float lambda, int reg_mode, double* out, void* stream);
+
+/* ---- The block solver: the same systems by exact block Gauss-Seidel over blocks of 32 features with a cached prediction per
+ * stored entry (the recurrence of cumf_als_update_block, cumf_free_capi.h), warm-started from `update`; every live row runs
+ * exactly `sweeps` >= 1 sweeps.  With s_u the weight of row u's unstored entries and q_e = w_e - s_u c_i, block pi_k takes
+ *   g = sum_e y_e[pi_k] (w_e r_e - q_e yhat_e),   H = sum_e q_e y_e[pi_k] y_e[pi_k]^T + s_u G[pi_k, pi_k] + reg I,
+ *   rhs = (g - s_u (G x)[pi_k]) - reg x[pi_k],    x[pi_k] += H^-1 rhs.
+ * q_e may be negative; H = s_u sum_unstored + sum_stored w + reg I stays positive definite and is eliminated without pivoting.
+ * One sweep is the exact solve at f <= 32, and the sweeps converge to it at every even 8 <= f <= 512.
+ * Scalar form: own_w0 == gather_w0 == NULL, s_u = w0, G = cumf_implicit_gram(gather), read only when w0 > 0 (NULL is fine at
+ * w0 == 0).  Rank-one form: both vectors given as cumf_als_update_weighted_rank1 takes them, w0 == 0, G =
+ * cumf_weighted_gram(gather, gather_w0); with (w0, 1) it returns the scalar form's bits.  route: CUMF_BLOCK_ROUTE_AUTO runs a
+ * row of at most 2048 entries on one wave in one launch and longer rows on per-segment kernels, CUMF_BLOCK_ROUTE_SEGMENTED every
+ * row on those.  Without a Gram term (scalar form, w0 == 0) the two routes give the same bits; with one they sum (G x) in
+ * different orders and differ in the last bits.  A row's result depends on the row and the route alone.
+ * Refused with hipErrorInvalidValue before any device call: a NULL plan or pointer, a plan whose f is odd, below 8 or above
+ * 512, an unknown reg_mode or route, sweeps < 1, w0 < 0 or NaN, G == NULL where a Gram term exists, one rank-one vector without
+ * the other, w0 != 0 beside them. */
+int cumf_als_update_weighted_block(const cumf_plan_t* plan, const int* colidx, const float* val, const float* wgt,
+                                   const float* gather, const float* G, const float* own_w0, const float* gather_w0,
+                                   float* update, float lambda, float w0, int reg_mode, int sweeps, int route, void* stream);
 
 #ifdef __cplusplus
 }
