@@ -33,6 +33,8 @@
   `update_weighted_rank1`, `weighted_rank1_loss`: the same with the rank-one weight a_u c_i on the unstored entry (u, i)
   (`WeightedALSEngine(unobserved=(a, c))`; `popularity_weights` gives eALS's c).  `update_weighted_block`: both forms by
   the block solver (`WeightedALSEngine(solver="block", cg_iters=sweeps)`), a row of at most 2048 entries in one launch.
+  `update_weighted_block_nonneg`: the same under x >= 0 (`nonnegative=True` on `WeightedALSEngine(solver="block")` and, on
+  the model's weighted form, `ImplicitALSEngine(solver="block")`): non-negative weighted and implicit ALS up to f = 512.
 
 There is no CPU path here: every call lands in a HIP kernel of libALS.so.
 """
@@ -1149,17 +1151,28 @@ class ImplicitALSEngine(_Engine):
     batches.  solver "cg" (warm-started, `cg_iters` steps; rows of at most 32 entries never form their system), "lu" or
     "cg_matfree" (the same CG recurrence, no row ever forms its system); reg "weighted" (lambda n_u, the default) or
     "plain" (lambda).  "cg" and "lu" take even 8 <= f <= 128, "cg_matfree" even 8 <= f <= 512; at 128 < f <= 512
-    solver "cg" runs "cg_matfree", the only CG there ("lu" and nonnegative=True stay limited to f <= 128).  solver "block"
+    solver "cg" runs "cg_matfree", the only CG there ("lu" stays limited to f <= 128).  solver "block"
     (even 8 <= f <= 512) is the iALS++ block solver: `cg_iters` sweeps of exact block Gauss-Seidel over blocks of 32
-    features per half-iteration -- the exact solve at f <= 32, and convergent to it for any f; it has no non-negative form."""
+    features per half-iteration -- the exact solve at f <= 32, and convergent to it for any f.  solver "block" with
+    nonnegative=True keeps every factor >= 0 at every even 8 <= f <= 512: each half-iteration is
+    `update_weighted_block_nonneg` on the weights 1 + alpha |r|, the targets (r > 0) and w0 = 1 (the weighted form of this
+    model), `cg_iters` sweeps, statistics in `nnls_stats`; nonnegative=True with any other solver materialises every system
+    (`update_implicit_nonneg`, f <= 128)."""
 
     def __init__(self, r, f: int, lambda_: float, alpha: float, solver="cg", cg_iters: int = 3, reg="weighted",
                  x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, nonnegative: bool = False):
         import torch
 
-        # nonnegative: every half-iteration is update_implicit_nonneg (materialise + NNLS); solver and cg_iters are unused
+        # nonnegative: every half-iteration is update_implicit_nonneg (materialise + NNLS; solver and cg_iters are unused), or
+        # with solver "block" update_weighted_block_nonneg on the model's weighted form
         self.nonnegative = bool(nonnegative)
-        if self.nonnegative:
+        self.block_nonneg = self.nonnegative and solver in (SOLVER_BLOCK, "block")
+        if self.block_nonneg:
+            if not implicit_available(f, solver) or int(cg_iters) < 1:
+                raise ValueError(f"solver 'block' with nonnegative=True takes even 8 <= f <= 512 and cg_iters (its sweeps) >= 1 "
+                                 f"(got f = {f}, cg_iters = {cg_iters})")
+            self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
+        elif self.nonnegative:
             _check_nonneg_f(f)
             self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=r.csr_indices.device)
         else:
@@ -1175,6 +1188,25 @@ class ImplicitALSEngine(_Engine):
         super().__init__(r, f, x_batch, theta_batch, chunk)
         self.csr_rowptr = r.csr_indptr.to(device=self.device, dtype=torch.int32).contiguous()
         self.G = torch.empty((f, f), dtype=torch.float32, device=self.device)
+        if self.block_nonneg:  # the weighted form, once: (targets (r > 0), weights 1 + alpha |r|) in CSR and in CSC order
+            self._csr_tw, self._csc_tw = (((d > 0).to(torch.float32), (1.0 + self.alpha * d.abs()).contiguous())
+                                          for d in (r.csr_data, r.csc_data))
+
+    def _half_block_nonneg(self, plans, colidx, tw, gather, update):
+        implicit_gram(gather, self.G)
+        for p in plans:
+            update_weighted_block_nonneg(p, colidx, tw[0], tw[1], gather, self.G, update, self.lam, 1.0, self.reg, self.cg_iters,
+                                         stats=self.nnls_stats)
+
+    def update_x(self):
+        if not self.block_nonneg:
+            return super().update_x()
+        self._half_block_nonneg(self.x_plans, self.r.csr_indices, self._csr_tw, self.thetaT, self.XT)
+
+    def update_theta(self):
+        if not self.block_nonneg:
+            return super().update_theta()
+        self._half_block_nonneg(self.t_plans, self.r.csc_indices, self._csc_tw, self.XT, self.thetaT)
 
     def _half(self, plans, colidx, val, gather, update):
         implicit_gram(gather, self.G)
@@ -1331,12 +1363,30 @@ def update_weighted_block(plan: Plan, colidx, val, wgt, gather, G, update, lambd
     otherwise G = implicit_gram(gather), read only when w0 > 0.  A row of at most 2048 entries runs on one wave in one launch,
     longer rows on per-segment kernels; route "segmented" sends every row there (the same bits without a Gram term, the last
     bits differ with one).  Rows without entries get 0."""
+    return _weighted_block("update_weighted_block", plan, colidx, val, wgt, gather, G, update, lambda_, w0, reg, sweeps, route,
+                           unobserved)
+
+
+def update_weighted_block_nonneg(plan: Plan, colidx, val, wgt, gather, G, update, lambda_: float, w0: float = 0.0,
+                                 reg="weighted", sweeps: int = 1, route="auto", unobserved=None, stats=None):
+    """`update_weighted_block` under x >= 0 (cumf_als_update_weighted_block_nonneg): every block step is the 32-wide
+    non-negative least-squares problem on the block's H and right-hand side, Gram term included, solved by block principal
+    pivoting on one wave from the passive set {x > 0}; G x and the cached predictions follow the constrained step.  One sweep
+    is the row's exact NNLS solution at f <= 32 and the sweeps converge to it at any even 8 <= f <= 512.  Same arguments and
+    routes; with w = 1, w0 = 0 the bits of `update_block_nonneg`.  stats: an optional int64 tensor [2] that is ADDED to:
+    (block steps not converged, 32 x 32 eliminations)."""
+    return _weighted_block("update_weighted_block_nonneg", plan, colidx, val, wgt, gather, G, update, lambda_, w0, reg, sweeps,
+                           route, unobserved, True, stats)
+
+
+def _weighted_block(who, plan, colidx, val, wgt, gather, G, update, lambda_, w0, reg, sweeps, route, unobserved, nonneg=False,
+                    stats=None):
     import torch
 
     if not weighted_available(plan.f):
-        raise ValueError(f"update_weighted_block takes even 8 <= f <= 512 (got f = {plan.f})")
+        raise ValueError(f"{who} takes even 8 <= f <= 512 (got f = {plan.f})")
     if int(sweeps) < 1:
-        raise ValueError(f"update_weighted_block takes sweeps >= 1 (got {sweeps})")
+        raise ValueError(f"{who} takes sweeps >= 1 (got {sweeps})")
     if route not in BLOCK_ROUTES:
         raise ValueError(f"unknown route {route!r} (auto | segmented)")
     w0 = _check_w0(w0)
@@ -1344,21 +1394,25 @@ def update_weighted_block(plan: Plan, colidx, val, wgt, gather, G, update, lambd
     if unobserved is not None:
         if w0 > 0:
             raise ValueError(f"unobserved=(own_w0, gather_w0) replaces w0: pass one of them (got w0 = {w0})")
-        own_w0 = _check_rank1_vec("update_weighted_block: own_w0", unobserved[0], update.shape[0], update.device)
-        gather_w0 = _check_rank1_vec("update_weighted_block: gather_w0", unobserved[1], gather.shape[0], gather.device)
+        own_w0 = _check_rank1_vec(f"{who}: own_w0", unobserved[0], update.shape[0], update.device)
+        gather_w0 = _check_rank1_vec(f"{who}: gather_w0", unobserved[1], gather.shape[0], gather.device)
     if (w0 > 0 or unobserved is not None) and G is None:
-        raise ValueError("update_weighted_block: w0 > 0 or unobserved weights need the Gram G of `gather`")
+        raise ValueError(f"{who}: w0 > 0 or unobserved weights need the Gram G of `gather`")
     if gather.dim() != 2 or update.dim() != 2 or gather.shape[1] != plan.f or update.shape[1] != plan.f:
-        raise ValueError(f"update_weighted_block: gather and update must be [rows, {plan.f}], the plan's f "
+        raise ValueError(f"{who}: gather and update must be [rows, {plan.f}], the plan's f "
                          f"(got {tuple(gather.shape)}, {tuple(update.shape)})")
     if G is not None and tuple(G.shape) != (plan.f, plan.f):
-        raise ValueError(f"update_weighted_block: G must be [{plan.f}, {plan.f}] (got {tuple(G.shape)})")
+        raise ValueError(f"{who}: G must be [{plan.f}, {plan.f}] (got {tuple(G.shape)})")
     if wgt.shape != val.shape:
-        raise ValueError(f"update_weighted_block: wgt must be parallel to val (got {tuple(wgt.shape)}, {tuple(val.shape)})")
-    _libmod.check(_libmod.load().cumf_als_update_weighted_block(
-        plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32), _dp(gather, torch.float32),
-        _dp(G, torch.float32), _dp(own_w0, torch.float32), _dp(gather_w0, torch.float32), _dp(update, torch.float32),
-        float(lambda_), w0, _reg_id(reg), int(sweeps), BLOCK_ROUTES[route], _stream()), "cumf_als_update_weighted_block")
+        raise ValueError(f"{who}: wgt must be parallel to val (got {tuple(wgt.shape)}, {tuple(val.shape)})")
+    args = (plan._h, _dp(colidx, torch.int32), _dp(val, torch.float32), _dp(wgt, torch.float32), _dp(gather, torch.float32),
+            _dp(G, torch.float32), _dp(own_w0, torch.float32), _dp(gather_w0, torch.float32), _dp(update, torch.float32),
+            float(lambda_), w0, _reg_id(reg), int(sweeps), BLOCK_ROUTES[route])
+    if nonneg:
+        _libmod.check(_libmod.load().cumf_als_update_weighted_block_nonneg(*args, _nnls_stats(stats), _stream()),
+                      "cumf_als_update_weighted_block_nonneg")
+    else:
+        _libmod.check(_libmod.load().cumf_als_update_weighted_block(*args, _stream()), "cumf_als_update_weighted_block")
     return update
 
 
@@ -1384,7 +1438,8 @@ class WeightedALSEngine(_Engine):
     `weights` (a device tensor parallel to r.csr_data, CSR entry order), every unstored entry is a target of 0 with the weight
     w0 >= 0.  Same shape as `ALSEngine`; every half-iteration is `update_weighted` (even 8 <= f <= 512; solver "cg", the
     default) or `update_weighted_block` (solver "block": `cg_iters` >= 1 counts its sweeps, which converge to the exact solve;
-    `block_route` as on ALSEngine), and with
+    `block_route` as on ALSEngine; nonnegative=True, with solver "block" only, keeps every factor >= 0 through
+    `update_weighted_block_nonneg`, statistics in `nnls_stats`), and with
     w0 > 0 it forms G = Y^T Y of the fixed side once, before its batches.  reg "weighted" (lambda n_u, the default) or "plain".
     w = 1, w0 = 0 is ALSEngine(solver="cg_matfree"); w = 1 + alpha |r| on ratings (r > 0) with w0 = 1 is
     ImplicitALSEngine(solver="cg_matfree").
@@ -1395,7 +1450,8 @@ class WeightedALSEngine(_Engine):
     for bit; `popularity_weights` gives the eALS column weights."""
 
     def __init__(self, r, weights, f: int, lambda_: float, w0: float = 0.0, reg="weighted", cg_iters: int = 6,
-                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, unobserved=None, solver="cg"):
+                 x_batch: int = 1, theta_batch: int = 1, chunk: int = 0, unobserved=None, solver="cg",
+                 nonnegative: bool = False):
         import torch
 
         if not weighted_available(f):
@@ -1404,6 +1460,9 @@ class WeightedALSEngine(_Engine):
             raise ValueError(f"unknown solver {solver!r} (cg | block)")
         if solver == "block" and int(cg_iters) < 1:
             raise ValueError(f"solver 'block' takes cg_iters (its sweeps) >= 1 (got {cg_iters})")
+        self.nonnegative = bool(nonnegative)
+        if self.nonnegative and solver != "block":
+            raise ValueError(f"nonnegative=True needs solver='block': solver {solver!r} has no non-negative form")
         self.block, self.block_route = solver == "block", "auto"
         self.lam, self.w0 = float(lambda_), _check_w0(w0)
         self.reg, self.cg_iters = _reg_id(reg), int(cg_iters)
@@ -1442,6 +1501,8 @@ class WeightedALSEngine(_Engine):
         self.csr_rowptr = r.csr_indptr.to(device=self.device, dtype=torch.int32).contiguous()
         self.G = torch.empty((f, f), dtype=torch.float32, device=self.device) \
             if (self.w0 > 0 or self.row_w0 is not None) else None
+        if self.nonnegative:
+            self.nnls_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
 
     @staticmethod
     def _unit_gather(own, gather):
@@ -1450,13 +1511,20 @@ class WeightedALSEngine(_Engine):
             return own, gather
         return (own * top).contiguous(), (gather / top).contiguous()
 
+    def _block(self, p, colidx, val, wgt, gather, update, w0, unobserved=None):
+        if self.nonnegative:
+            update_weighted_block_nonneg(p, colidx, val, wgt, gather, self.G, update, self.lam, w0, self.reg, self.cg_iters,
+                                         self.block_route, unobserved, self.nnls_stats)
+        else:
+            update_weighted_block(p, colidx, val, wgt, gather, self.G, update, self.lam, w0, self.reg, self.cg_iters,
+                                  self.block_route, unobserved)
+
     def _half_weighted(self, plans, colidx, val, wgt, gather, update, own_w0=None, gather_w0=None):
         if own_w0 is not None:  # rank-one weights on the unstored entries
             weighted_gram(gather, gather_w0, self.G)
             for p in plans:
                 if self.block:
-                    update_weighted_block(p, colidx, val, wgt, gather, self.G, update, self.lam, 0.0, self.reg, self.cg_iters,
-                                          self.block_route, (own_w0, gather_w0))
+                    self._block(p, colidx, val, wgt, gather, update, 0.0, (own_w0, gather_w0))
                     continue
                 update_weighted_rank1(p, colidx, val, wgt, gather, self.G, own_w0, gather_w0, update, self.lam, self.reg,
                                       self.cg_iters)
@@ -1465,8 +1533,7 @@ class WeightedALSEngine(_Engine):
             implicit_gram(gather, self.G)
         for p in plans:
             if self.block:
-                update_weighted_block(p, colidx, val, wgt, gather, self.G, update, self.lam, self.w0, self.reg, self.cg_iters,
-                                      self.block_route)
+                self._block(p, colidx, val, wgt, gather, update, self.w0)
                 continue
             update_weighted(p, colidx, val, wgt, gather, self.G, update, self.lam, self.w0, self.reg, self.cg_iters)
 

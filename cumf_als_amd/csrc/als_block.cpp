@@ -192,10 +192,11 @@ int cumf::update_block_explicit(cumf_plan* p, const int* colidx, const float* va
 
 // The weighted half-iteration: update_block_explicit's routing on the weighted kernels.  Without a Gram term (w0 == 0 and no
 // rank-one vectors) the fused kernel is block_fused_kernel at kFreeWeightArray and the long rows end in block_row_free_kernel;
-// with one, block_fused_gram_kernel and the scaled block_row_kernel over the long rows' list.
+// with one, block_fused_gram_kernel and the scaled block_row_kernel over the long rows' list.  nonneg: the same launches at
+// kNonneg; stats as update_block_explicit takes them.
 int cumf::update_block_weighted(cumf_plan* p, const int* colidx, const float* val, const float* wgt, const float* gather,
                                 const float* G, const float* own_w0, const float* gather_w0, float* update, float lambda,
-                                float w0, int reg_mode, int sweeps, int route, hipStream_t s) {
+                                float w0, int reg_mode, int sweeps, int route, bool nonneg, long long* stats, hipStream_t s) {
   const FreeSegLists* fl = nullptr;
   int rc = plan_free_lists(p, &fl);
   if (rc) return rc;
@@ -243,21 +244,22 @@ int cumf::update_block_weighted(cumf_plan* p, const int* colidx, const float* va
     CUMF_HIP_CHECK(launch_block_open(b, s));
     for (int sweep = 0; sweep < sweeps; ++sweep)
       for (int k = 0; k < nb; ++k)
-        CUMF_HIP_CHECK(launch_block_step_weighted(b, l->d_lrow, l->d_lrow_pseg0, l->n_lrow, k, sweep > 0 || k > 0, sweep == 0, mode, s));
+        CUMF_HIP_CHECK(launch_block_step_weighted(b, l->d_lrow, l->d_lrow_pseg0, l->n_lrow, k, sweep > 0 || k > 0, sweep == 0, mode,
+                                                 nonneg, stats, s));
   }
   for (int c = kBlockClasses - 1; c >= 0; --c)
     if (mode == kBlockWeightPlain)
-      CUMF_HIP_CHECK(launch_block_fused_weighted(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, s));
+      CUMF_HIP_CHECK(launch_block_fused_weighted(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, nonneg, stats, s));
     else
-      CUMF_HIP_CHECK(launch_block_fused_gram(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, mode, s));
+      CUMF_HIP_CHECK(launch_block_fused_gram(a, l->d_class_rows[c], l->n_class[c], kBlockCap[c], sweeps, mode, nonneg, stats, s));
   return 0;
 }
 
-extern "C" int cumf_als_update_weighted_block(const cumf_plan_t* pc, const int* colidx, const float* val, const float* wgt,
-                                              const float* gather, const float* G, const float* own_w0, const float* gather_w0,
-                                              float* update, float lambda, float w0, int reg_mode, int sweeps, int route,
-                                              void* stream) {
-  const char* who = "cumf_als_update_weighted_block";
+// the two weighted entry points: one set of refusals
+static int weighted_block_entry(const char* who, const cumf_plan_t* pc, const int* colidx, const float* val, const float* wgt,
+                                const float* gather, const float* G, const float* own_w0, const float* gather_w0, float* update,
+                                float lambda, float w0, int reg_mode, int sweeps, int route, bool nonneg, long long* stats,
+                                void* stream) {
   if (!pc || !colidx || !val || !wgt || !gather || !update) {
     fprintf(stderr, "%s: plan, colidx, val, wgt, gather and update must not be NULL\n", who);
     return (int)hipErrorInvalidValue;
@@ -285,7 +287,23 @@ extern "C" int cumf_als_update_weighted_block(const cumf_plan_t* pc, const int* 
   }
   ScratchLease lease;
   return update_block_weighted(const_cast<cumf_plan*>(pc), colidx, val, wgt, gather, G, own_w0, gather_w0, update, lambda, w0,
-                               reg_mode, sweeps, route, static_cast<hipStream_t>(stream));
+                               reg_mode, sweeps, route, nonneg, stats, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int cumf_als_update_weighted_block(const cumf_plan_t* pc, const int* colidx, const float* val, const float* wgt,
+                                              const float* gather, const float* G, const float* own_w0, const float* gather_w0,
+                                              float* update, float lambda, float w0, int reg_mode, int sweeps, int route,
+                                              void* stream) {
+  return weighted_block_entry("cumf_als_update_weighted_block", pc, colidx, val, wgt, gather, G, own_w0, gather_w0, update, lambda,
+                              w0, reg_mode, sweeps, route, false, nullptr, stream);
+}
+
+extern "C" int cumf_als_update_weighted_block_nonneg(const cumf_plan_t* pc, const int* colidx, const float* val, const float* wgt,
+                                                     const float* gather, const float* G, const float* own_w0,
+                                                     const float* gather_w0, float* update, float lambda, float w0, int reg_mode,
+                                                     int sweeps, int route, long long* stats, void* stream) {
+  return weighted_block_entry("cumf_als_update_weighted_block_nonneg", pc, colidx, val, wgt, gather, G, own_w0, gather_w0, update,
+                              lambda, w0, reg_mode, sweeps, route, true, stats, stream);
 }
 
 extern "C" int cumf_block_available(int f) { return block_f_ok(f); }

@@ -21,7 +21,9 @@
 // The non-negative explicit solver (cumf_als_update_block_nonneg) changes the block step alone: with c = rhs + H x[pi_k],
 //   z = argmin_{z >= 0} 1/2 z^T H z - c^T z;   d = z - x[pi_k];   x[pi_k] = z
 // -- block coordinate descent on the row's strictly convex QP, which converges to the row's NNLS solution and is that solution
-// after one sweep at f <= 32.  Same kernels (template flag kNonneg), lists, classes and scratch.
+// after one sweep at f <= 32.  Same kernels (template flag kNonneg), lists, classes and scratch.  The weighted solver
+// (cumf_als_update_weighted_block_nonneg) takes the same step on its own H and rhs below, Gram term included: (G x)[pi_k] is
+// kept current with d = z - x[pi_k] exactly as with the unconstrained d.
 #ifndef CUMF_ALS_BLOCK_H_
 #define CUMF_ALS_BLOCK_H_
 
@@ -117,20 +119,22 @@ hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const
 // q_e may be negative; H = s_u sum_unstored + sum_stored w + reg I stays positive definite.  BlockWeightMode: where s_u and
 // q_e come from; kBlockWeightPlain is the call without any Gram term (w0 == 0, no rank-one vectors: q_e = w_e).
 enum BlockWeightMode { kBlockWeightPlain = 0, kBlockWeightScalar = 1, kBlockWeightRank1 = 2 };
-// rows[0 .. nrows) of at most `cap` entries, one wave per row, kBlockWeightPlain: block_fused_kernel at kFreeWeightArray
-hipError_t launch_block_fused_weighted(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps,
-                                       hipStream_t stream);
+// rows[0 .. nrows) of at most `cap` entries, one wave per row, kBlockWeightPlain: block_fused_kernel at kFreeWeightArray.
+// nonneg, stats: as launch_block_fused takes them, here and in the two launches below
+hipError_t launch_block_fused_weighted(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, bool nonneg,
+                                       long long* stats, hipStream_t stream);
 // ... with the Gram term (als_block_gram.hip: block_fused_gram_kernel); a.G is required
 hipError_t launch_block_fused_gram(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, int mode,
-                                   hipStream_t stream);
+                                   bool nonneg, long long* stats, hipStream_t stream);
 // block step k of the rows `rows` on a's segment lists: block_sparse_kernel at the mode's weights, then block_row_free_kernel
 // (kBlockWeightPlain) or the Gram row pass block_row_kernel with the row's scale, 32 listed rows per workgroup
 hipError_t launch_block_step_weighted(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
-                                      int have_prev, int first, int mode, hipStream_t stream);
+                                      int have_prev, int first, int mode, bool nonneg, long long* stats, hipStream_t stream);
 // One weighted block-solver half-iteration on the plan's rows (als_block.cpp), routed as update_block_explicit routes.
 CUMF_LOCAL int update_block_weighted(cumf_plan* p, const int* colidx, const float* val, const float* wgt, const float* gather,
                                      const float* G, const float* own_w0, const float* gather_w0, float* update, float lambda,
-                                     float w0, int reg_mode, int sweeps, int route, hipStream_t stream);
+                                     float w0, int reg_mode, int sweeps, int route, bool nonneg, long long* stats,
+                                     hipStream_t stream);
 // One explicit block-solver half-iteration on the plan's rows (als_block.cpp): at most kBlockClasses fused launches, and
 // 1 + 2 sweeps ceil(f / B) launches over the long rows where the plan has any.  The caller holds the ScratchLease.
 CUMF_LOCAL int update_block_explicit(cumf_plan* p, const int* colidx, const float* val, const float* gather, float* update,

@@ -2,7 +2,7 @@
 // segment lists (als_free.h: one wave per segment of at most kFreeSeg entries, so rows of any length work), and the explicit
 // block solver's route for rows longer than one segment: block_sparse_kernel at kFreeWeightNone and block_row_free_kernel, the
 // row pass without the Gram term; and the weighted block solver's (kFreeWeightArray / kFreeWeightRank1; the row pass with the
-// row's scale on the Gram term, over a row list).  The device functions they share with the fused kernels are als_block_core.h.
+// row's scale on the Gram term, over a row list; kNonneg: the 32-wide NNLS in place of the elimination).  The device functions they share with the fused kernels are als_block_core.h.
 //   block_open_kernel    one wave per segment: yhat_e = t_e . x (lane l holds features l + 64 q; the transposing wave reduction
 //                        of als_device.h);
 //   block_sparse_kernel  one wave per segment and block step: the block's 128-byte slice of each gathered row lands directly in
@@ -94,9 +94,17 @@ __global__ __launch_bounds__(kFreeThreads) void block_sparse_kernel(const BlockA
 // own_w0[u] where that is given, else w0 -- gx and the live part of gpp are multiplied where they are used, as kScale of
 // free_gram_rows multiplies G v; the identity that pads a ragged block is not scaled.  Without kScaled the expressions are
 // the implicit model's own.
-template <int Q, int B, bool kScaled>
+// kNonneg: the block step under x >= 0.  The MFMA phase is the workgroup's last common work: after its barrier every wave owns
+// its rows (wave, wave + 4, ..) and its tile hs[wave] and meets no further barrier, so the pivoting loop of block_nnls32, whose
+// trip count differs from row to row, holds up only the wave it runs on -- the other three go on through their own rows and
+// retire while it pivots; only the workgroup's LDS stays allocated until the last of them ends.  The lanes write the whole
+// H = (h + reg) + s_u G[pi_k, pi_k] back into the wave's tile (the sum the elimination takes in registers), block_nnls32 re-reads
+// it per passive set, x[pi_k] = z and d = z - x[pi_k].  gx, gpp and vs are read only, so a row's result depends on the row
+// alone.  stats as in block_fused_kernel, summed over the wave's rows.
+template <int Q, int B, bool kScaled, bool kNonneg>
 __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs a, const int* rows, const int* pseg0,
-                                                                 long long nrows, int k, int first) {
+                                                                 long long nrows, int k, int first,
+                                                                 unsigned long long* stats) {
   static_assert(B == 32, "two 16-row tiles x two 16-column tiles, one per wave; one matrix row per lane of a half wave");
   constexpr int P = 64 * Q + 4;  // LDS pitch of the staged x: the 16 rows one MFMA operand reads start 4 banks apart
   constexpr int HP = kBlockTilePitch;
@@ -142,6 +150,7 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
   }
   __syncthreads();
   float* Hs = hs[wave];
+  [[maybe_unused]] unsigned n_failed = 0, n_elim = 0;
   for (int rr = wave; rr < nr; rr += 4) {
     int i = lane & 31;  // the matrix row of this lane (the upper half wave repeats the lower and writes nothing)
     const long long row = row_of(rr);
@@ -172,14 +181,37 @@ __global__ __launch_bounds__(kFreeThreads) void block_row_kernel(const BlockArgs
       for (int j = 0; j < B; ++j) hrow[j] = Hs[i * HP + j] + gpp[i * HP + j];
       rhs = i < bw ? (gp - gx[rr * HP + i]) - reg * xv : 0.f;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();  // Hs is free for the wave's next row
-    const float dv = block_solve32(hrow, rhs, i);
-    if (lane < B) {
-      if (lane < bw) a.x[(size_t)row * f + c0 + lane] = xv + dv;
-      a.d[(size_t)row * B + lane] = dv;
+    if constexpr (kNonneg) {
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();  // both half waves have read row i
+      if (lane < B) {
+#pragma unroll
+        for (int j = 0; j < B; ++j) Hs[i * HP + j] = hrow[j];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      const float z = block_nnls32(Hs, i, bw, rhs, xv, n_failed, n_elim);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();  // Hs is free for the wave's next row
+      if (lane < B) {
+        if (lane < bw) a.x[(size_t)row * f + c0 + lane] = z;
+        a.d[(size_t)row * B + lane] = z - xv;
+      }
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();  // Hs is free for the wave's next row
+      const float dv = block_solve32(hrow, rhs, i);
+      if (lane < B) {
+        if (lane < bw) a.x[(size_t)row * f + c0 + lane] = xv + dv;
+        a.d[(size_t)row * B + lane] = dv;
+      }
     }
   }
+  if constexpr (kNonneg)
+    if (stats && lane == 0) {
+      if (n_failed) atomicAdd(stats, (unsigned long long)n_failed);
+      if (n_elim) atomicAdd(stats + 1, (unsigned long long)n_elim);
+    }
 }
 
 // ---- the row pass of the explicit model, whose A = T^T T + reg I has no Gram term: rhs = g - reg x[pi_k], nothing is staged
@@ -253,9 +285,9 @@ hipError_t launch_block_step(const BlockArgs& a, int k, int have_prev, int first
     if (e != hipSuccess) return e;
   }
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
-    return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth, false>,
+    return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth, false, false>,
                               dim3(free_grid(a.rows, kFreeRows, 1ll << 30)), dim3(kFreeThreads), 0, stream, a,
-                              (const int*)nullptr, (const int*)nullptr, a.rows, k, first);
+                              (const int*)nullptr, (const int*)nullptr, a.rows, k, first, (unsigned long long*)nullptr);
   });
 }
 
@@ -273,8 +305,9 @@ hipError_t launch_block_step_explicit(const BlockArgs& a, const int* rows, const
 }
 
 hipError_t launch_block_step_weighted(const BlockArgs& a, const int* rows, const int* pseg0, long long nrows, int k,
-                                      int have_prev, int first, int mode, hipStream_t stream) {
+                                      int have_prev, int first, int mode, bool nonneg, long long* stats, hipStream_t stream) {
   if (nrows <= 0) return hipSuccess;
+  auto* st = reinterpret_cast<unsigned long long*>(stats);
   if (a.nseg > 0) {
     const hipError_t e = launch_kernel(mode == kBlockWeightRank1 ? block_sparse_kernel<kBlockWidth, kFreeWeightRank1>
                                                                  : block_sparse_kernel<kBlockWidth, kFreeWeightArray>,
@@ -282,12 +315,13 @@ hipError_t launch_block_step_weighted(const BlockArgs& a, const int* rows, const
     if (e != hipSuccess) return e;
   }
   if (mode == kBlockWeightPlain)
-    return launch_item_kernel(block_row_free_kernel<kBlockWidth, false, true>, dim3(free_grid(nrows, 4, 1ll << 30)),
-                              dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows, k, first, (unsigned long long*)nullptr);
+    return launch_item_kernel(nonneg ? block_row_free_kernel<kBlockWidth, true, true> : block_row_free_kernel<kBlockWidth, false, true>,
+                              dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows, k, first, st);
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
-    return launch_item_kernel(block_row_kernel<decltype(qc)::value, kBlockWidth, true>,
+    constexpr int Q = decltype(qc)::value;
+    return launch_item_kernel(nonneg ? block_row_kernel<Q, kBlockWidth, true, true> : block_row_kernel<Q, kBlockWidth, true, false>,
                               dim3(free_grid(nrows, kFreeRows, 1ll << 30)), dim3(kFreeThreads), 0, stream, a, rows, pseg0, nrows,
-                              k, first);
+                              k, first, st);
   });
 }
 

@@ -124,13 +124,15 @@ hipError_t launch_block_fused(const BlockArgs& a, const int* rows, long long nro
   });
 }
 
-hipError_t launch_block_fused_weighted(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps,
-                                       hipStream_t stream) {
+hipError_t launch_block_fused_weighted(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, bool nonneg,
+                                       long long* stats, hipStream_t stream) {
   if (nrows <= 0) return hipSuccess;
   const size_t lds = 4 * (size_t)(kBlockWidth * kBlockTilePitch + cap) * sizeof(float);
+  auto* st = reinterpret_cast<unsigned long long*>(stats);
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
-    return launch_item_kernel(block_fused_kernel<decltype(qc)::value, false, kFreeWeightArray>, dim3(free_grid(nrows, 4, 1ll << 30)),
-                              dim3(kFreeThreads), lds, stream, a, rows, nrows, cap, sweeps, (unsigned long long*)nullptr);
+    constexpr int Q = decltype(qc)::value;
+    return launch_item_kernel(nonneg ? block_fused_kernel<Q, true, kFreeWeightArray> : block_fused_kernel<Q, false, kFreeWeightArray>,
+                              dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), lds, stream, a, rows, nrows, cap, sweeps, st);
   });
 }
 

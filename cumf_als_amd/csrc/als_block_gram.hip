@@ -45,9 +45,14 @@ __device__ __forceinline__ void block_gram_axpy(const float* G, int f, int j0, i
 }
 
 // kWeight: kFreeWeightArray (s_u = a.w0) or kFreeWeightRank1 (s_u = a.own_w0[row])
-template <int Q, FreeWeight kWeight>
+// kNonneg: the block step under x >= 0.  The tile already holds the whole H = (h + reg) + s_u G[pi_k, pi_k], so block_nnls32
+// runs on it as it does in block_fused_kernel: c = rhs + H x[pi_k] from the lane's tile row and the x[pi_k] the shuffle below
+// fetched, the passive set in SGPRs, every masked system re-read from the tile, which therefore stays live through the step
+// (no row copy in registers: hrow is not loaded).  x[pi_k] = z, d = z - x[pi_k]; u += G[:, pi_k] d and the deferred
+// yhat += t[pi_k] . d then run on that d as on the unconstrained one.  stats as in block_fused_kernel.
+template <int Q, FreeWeight kWeight, bool kNonneg>
 __global__ __launch_bounds__(kFreeThreads) void block_fused_gram_kernel(const BlockArgs a, const int* rows, long long nrows,
-                                                                        int cap, int sweeps) {
+                                                                        int cap, int sweeps, unsigned long long* stats) {
   static_assert(kWeight == kFreeWeightArray || kWeight == kFreeWeightRank1, "the weighted clients");
   constexpr int B = kBlockWidth, HP = kBlockTilePitch;
   extern __shared__ float lds[];
@@ -84,6 +89,7 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_gram_kernel(const Bl
     block_gram_axpy<Q>(a.G, f, 64 * q, cnt, v[q], lane, u);
   });
   float dv = 0.f;  // lanes 0..31 and again 32..63: the step of the block solved last
+  [[maybe_unused]] unsigned n_failed = 0, n_elim = 0;
   for (int sweep = 0; sweep < sweeps; ++sweep)
     for (int k = 0; k < nb; ++k) {
       const int have_prev = sweep > 0 || k > 0;
@@ -124,8 +130,8 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_gram_kernel(const Bl
       for (int m = 0; m < B / 2; ++m) Hs[(2 * m + (lane >> 5)) * HP + i] += gpp[m];
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
-      float hrow[B];
-      block_tile_row<false>(Hs, i, bw, hrow);
+      [[maybe_unused]] float hrow[B];
+      if constexpr (!kNonneg) block_tile_row<false>(Hs, i, bw, hrow);
       // x[pi_k] and (G x)[pi_k]: register k >> 1, lanes 32 (k & 1) ..; the solve wants feature c0 + i in lane i of both halves
       float xk = 0.f, uk = 0.f;
 #pragma unroll
@@ -134,29 +140,42 @@ __global__ __launch_bounds__(kFreeThreads) void block_fused_gram_kernel(const Bl
       const float xv = i < bw ? xs : 0.f;
       const float gp = i < 16 ? g0 : g1;  // g[i]: lane groups 1 and 3 hold g[16 + i16] in g1
       const float rhs = i < bw ? (gp - su * us) - reg * xv : 0.f;
+      [[maybe_unused]] float z = 0.f;
+      if constexpr (kNonneg) z = block_nnls32(Hs, i, bw, rhs, xv, n_failed, n_elim);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();  // Hs is free for the next block
-      dv = block_solve32(hrow, rhs, i);
+      if constexpr (kNonneg) dv = z - xv;
+      else dv = block_solve32(hrow, rhs, i);
       const bool mine = (lane >> 5) == (k & 1) && i < bw;
 #pragma unroll
-      for (int q = 0; q < Q; ++q) v[q] = (mine && q == (k >> 1)) ? v[q] + dv : v[q];
+      for (int q = 0; q < Q; ++q) v[q] = (mine && q == (k >> 1)) ? (kNonneg ? z : v[q] + dv) : v[q];
       // u += G[:, pi_k] d (G is symmetric: rows c0 .. c0 + bw - 1); nothing reads u after the very last step
       if (sweep + 1 < sweeps || k + 1 < nb) block_gram_axpy<Q>(a.G, f, c0, bw, dv, lane, u);
     }
 #pragma unroll
   for (int q = 0; q < Q; ++q)
     if (lane + 64 * q < f) xrow[lane + 64 * q] = v[q];
+  if constexpr (kNonneg)
+    if (stats && lane == 0) {
+      if (n_failed) atomicAdd(stats, (unsigned long long)n_failed);
+      if (n_elim) atomicAdd(stats + 1, (unsigned long long)n_elim);
+    }
 }
 
 hipError_t launch_block_fused_gram(const BlockArgs& a, const int* rows, long long nrows, int cap, int sweeps, int mode,
-                                   hipStream_t stream) {
+                                   bool nonneg, long long* stats, hipStream_t stream) {
   if (nrows <= 0) return hipSuccess;
   const size_t lds = 4 * (size_t)(kBlockWidth * kBlockTilePitch + cap) * sizeof(float);
+  auto* st = reinterpret_cast<unsigned long long*>(stats);
   return with_nb<1, 8>((a.f + 63) / 64, [&](auto qc) {
     constexpr int Q = decltype(qc)::value;
-    return launch_item_kernel(mode == kBlockWeightRank1 ? block_fused_gram_kernel<Q, kFreeWeightRank1>
-                                                        : block_fused_gram_kernel<Q, kFreeWeightArray>,
-                              dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), lds, stream, a, rows, nrows, cap, sweeps);
+    auto go = [&](auto kernel) {
+      return launch_item_kernel(kernel, dim3(free_grid(nrows, 4, 1ll << 30)), dim3(kFreeThreads), lds, stream, a, rows, nrows,
+                                cap, sweeps, st);
+    };
+    if (mode == kBlockWeightRank1)
+      return nonneg ? go(block_fused_gram_kernel<Q, kFreeWeightRank1, true>) : go(block_fused_gram_kernel<Q, kFreeWeightRank1, false>);
+    return nonneg ? go(block_fused_gram_kernel<Q, kFreeWeightArray, true>) : go(block_fused_gram_kernel<Q, kFreeWeightArray, false>);
   });
 }
 

@@ -26,9 +26,9 @@
  * the default stream), 0 on success or a HIP error code after printing the reason to stderr, no CPU fallback.  Plans are the
  * cumf_plan_t of cumf_als_capi.h; a row's result does not depend on the plan's chunks, on the batch cuts or on the other
  * rows, and every result is bit-identical from run to run (fixed-order sums, no float atomics).
- * Scope: one GPU, the unbiased unconstrained model; the CG above, or the block solver at the end of this file, whose sweeps
+ * Scope: one GPU, the unbiased model; the CG above, or the block solver at the end of this file, whose sweeps
  * converge to the exact solve.  Not covered: LU or any materialised weighted system, a regulariser lambda sum_i w_ui, biases
- * or non-negativity combined with weights, cumf_doALS, several GPUs.
+ * combined with weights, non-negativity with the CG (the block solver has it), cumf_doALS, several GPUs.
  */
 #ifndef CUMF_WEIGHTED_CAPI_H_
 #define CUMF_WEIGHTED_CAPI_H_
@@ -113,6 +113,20 @@ int cumf_weighted_rank1_loss(const int* rowptr, const int* colidx, const float* 
 int cumf_als_update_weighted_block(const cumf_plan_t* plan, const int* colidx, const float* val, const float* wgt,
                                    const float* gather, const float* G, const float* own_w0, const float* gather_w0,
                                    float* update, float lambda, float w0, int reg_mode, int sweeps, int route, void* stream);
+
+/* cumf_als_update_weighted_block under x >= 0 (Spark MLlib's `nonnegative` on the weighted, implicit, eALS- or popularity-weighted
+ * model): the block step becomes the 32-wide non-negative least-squares problem of cumf_als_update_block_nonneg on the H and
+ * rhs above -- with c = rhs + H x[pi_k],
+ *   z = argmin_{z >= 0} 1/2 z^T H z - c^T z,   x[pi_k] = z,
+ * by block principal pivoting from the passive set {x[pi_k] > 0}; (G x) and the cached predictions follow d = z - x[pi_k].
+ * Block coordinate descent on the row's strictly convex problem: one sweep is the row's exact NNLS solution at f <= 32, and
+ * the sweeps converge to it at every even 8 <= f <= 512.  Same arguments, routes and refusals; with w = 1, w0 = 0 the bits of
+ * cumf_als_update_block_nonneg, and w = 1 + alpha |r|, val = (r > 0), w0 = 1 is non-negative implicit feedback.
+ * stats: NULL or a device int64[2] that is ADDED to: (block steps not converged, 32 x 32 eliminations). */
+int cumf_als_update_weighted_block_nonneg(const cumf_plan_t* plan, const int* colidx, const float* val, const float* wgt,
+                                          const float* gather, const float* G, const float* own_w0, const float* gather_w0,
+                                          float* update, float lambda, float w0, int reg_mode, int sweeps, int route,
+                                          long long* stats, void* stream);
 
 #ifdef __cplusplus
 }
