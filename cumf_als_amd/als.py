@@ -13,7 +13,7 @@
   GPUs form together (`cumf_als_amd.dist_implicit`).
 * `nnls_solve`, `update_nonneg`, `update_implicit_nonneg` (include/cumf_nnls_capi.h): non-negative least squares on
   materialised systems by block principal pivoting; both engines take `nonnegative=True` to keep every factor >= 0.
-* `topk`, `ranking_metrics` (include/cumf_topk_capi.h): the k best candidates per query, scored by a fused HIP kernel
+* `topk`, `ranking_metrics` (include/cumf_topk_capi.h): the k <= 2048 best candidates per query, scored by a fused HIP kernel
   that never writes the score matrix, and precision / recall / NDCG@k against held-out entries; both engines expose them
   as `recommend(k, side)` and `ranking_metrics(k, side)`.
 * `heldout_ranks`, `rank_metrics` (include/cumf_rank_capi.h): the rank of every held-out entry among all eligible
@@ -682,6 +682,13 @@ def topk_available(f: int, k: int) -> bool:
     return bool(_libmod.load().cumf_topk_available(int(f), int(k)))
 
 
+_TOPK_NARROW_K = 128  # cumf_topk's limit; `topk` takes larger k to cumf_topk_wide
+
+
+def topk_wide_available(f: int, k: int) -> bool:
+    return bool(_libmod.load().cumf_topk_wide_available(int(f), int(k)))
+
+
 def _rowptr(rowptr):
     import torch
 
@@ -700,7 +707,8 @@ def _exclusion(exclude):
 
 
 def topk(query, cand, k: int, exclude=None, out=None):
-    """The k best candidates of every query row (cumf_topk): `query` rows x f and `cand` ncand x f fp32 on the device, the
+    """The k best candidates of every query row (cumf_topk up to k = 128, cumf_topk_wide above, up to 2048): `query` rows x f
+    and `cand` ncand x f fp32 on the device, the
     score of a candidate the fp32 fmaf chain of the dot product in increasing feature order.  `exclude` is an optional
     (rowptr, colidx) CSR of candidate indices per query (ascending within each row) that are never returned.  Returns
     (ids int32, scores fp32), rows x k each, best first (ties: lower index first); missing slots are -1 / -inf."""
@@ -714,9 +722,10 @@ def topk(query, cand, k: int, exclude=None, out=None):
                torch.empty((rows, k), dtype=torch.float32, device=query.device))
     ids, scores = out
     rp, rp64, ci = _exclusion(exclude)
-    _libmod.check(_libmod.load().cumf_topk(
+    name = "cumf_topk" if int(k) <= _TOPK_NARROW_K else "cumf_topk_wide"
+    _libmod.check(getattr(_libmod.load(), name)(
         _dp(query, torch.float32), rows, _dp(cand, torch.float32), int(cand.shape[0]), f, rp, rp64, ci, int(k),
-        _dp(ids, torch.int32), _dp(scores, torch.float32), _stream()), "cumf_topk")
+        _dp(ids, torch.int32), _dp(scores, torch.float32), _stream()), name)
     return ids, scores
 
 

@@ -1,6 +1,6 @@
 // als_topk.cpp -- host side of top-k recommendation and ranking metrics (include/cumf_topk_capi.h): argument checks, scratch,
 // launches; and score_setup, the set-up every scoring launch shares (als_rank.cpp too): the slab cut (topk_cut, als_topk.h) and
-// the common arguments.  Kernels: als_topk.hip.
+// the common arguments.  Kernels: als_topk.hip, and als_topk_wide.hip for cumf_topk_wide (k above 128).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +14,9 @@ using namespace cumf;
 namespace {
 
 bool topk_ok(int f, int k) { return f >= 1 && f <= kTopkMaxF && k >= 1 && k <= kTopkMaxK; }
+bool topk_wide_ok(int f, int k) { return f >= 1 && f <= kTopkMaxF && k >= 1 && k <= kTopkWideMaxK; }
+// What the lists of cumf_topk_wide may take of the scratch pool: two workgroups on each of 256 CUs need 1.1 GiB at k = 2048.
+constexpr size_t kTopkWideWorkBytes = (size_t)2 << 30;
 
 }  // namespace
 
@@ -70,6 +73,39 @@ extern "C" int cumf_topk(const float* Q, long rows, const float* C, long ncand, 
   if (rc) return rc;
   CUMF_HIP_CHECK(launch_topk_score(a, grid, s));
   if (a.nslab > 1) CUMF_HIP_CHECK(launch_topk_merge(a.part, rows, k, a.nslab, ids, scores, s));
+  return 0;
+}
+
+extern "C" int cumf_topk_wide_available(int f, int k) { return topk_wide_ok(f, k); }
+
+// cumf_topk for k up to kTopkWideMaxK: the same set-up and cut, the kernels of als_topk_wide.hip.  The lists live in the
+// workgroups' scratch areas, kTopkQB x (k + kTopkBuf) keys each (2.2 MB at k = 2048); the persistent grid shrinks until they
+// fit kTopkWideWorkBytes (the kernel strides over the items, so the result does not change).
+extern "C" int cumf_topk_wide(const float* Q, long rows, const float* C, long ncand, int f, const void* excl_rowptr,
+                              int rowptr_is_64, const int* excl_colidx, int k, int* ids, float* scores, void* stream) {
+  TopkArgs a{};
+  long long grid = 0;
+  int rc = (int)hipErrorInvalidValue;
+  if (topk_wide_ok(f, k) && (rows <= 0 || (ids && scores)))
+    rc = score_setup(&a, Q, rows, C, ncand, f, excl_rowptr, rowptr_is_64, excl_colidx, topk_wide_score_occupancy, &grid);
+  if (rc == (int)hipErrorInvalidValue)
+    fprintf(stderr,
+            "cumf_topk_wide: needs 1 <= f <= %d (got %d), 1 <= k <= %d (got %d), rows >= 0, 0 <= ncand < 2^31, the tables and "
+            "outputs, and both exclusion arrays or neither\n",
+            kTopkMaxF, f, kTopkWideMaxK, k);
+  if (rc || !grid) return rc;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchLease lease;
+  a.k = k;
+  a.ids = ids;
+  a.scores = scores;
+  const size_t area = (size_t)kTopkQB * (k + kTopkBuf);  // keys per workgroup
+  grid = std::min<long long>(grid, std::max<size_t>(1, kTopkWideWorkBytes / (area * sizeof(unsigned long long))));
+  rc = scratch(s, kScratchTopkWork, (size_t)grid * area, &a.work);
+  if (!rc && a.nslab > 1) rc = scratch(s, kScratchTopkPart, (size_t)a.nslab * rows * k, &a.part);
+  if (rc) return rc;
+  CUMF_HIP_CHECK(launch_topk_wide_score(a, grid, s));
+  if (a.nslab > 1) CUMF_HIP_CHECK(launch_topk_wide_merge(a.part, rows, k, a.nslab, ids, scores, s));
   return 0;
 }
 

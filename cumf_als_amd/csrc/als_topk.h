@@ -18,6 +18,7 @@ constexpr int kTopkJC = 128;              // features per LDS chunk
 constexpr int kTopkPitch = kTopkJC + 4;   // LDS row pitch: the 16 rows one k-group reads start 4 banks apart
 constexpr int kTopkBuf = 128;             // survivor buffer per query (merged when above kTopkBuf - kTopkNC)
 constexpr int kTopkMaxK = 128;
+constexpr int kTopkWideMaxK = 2048;       // cumf_topk_wide (als_topk_wide.hip): the list in scratch, merged by rank
 constexpr int kTopkMaxF = 512;
 // What the scoring kernels share (als_score.h): the two tables, the exclusion CSR and the cut.  TopkArgs and RankArgs
 // (als_rank.h) extend it; score_setup fills it.
@@ -46,6 +47,11 @@ int topk_score_occupancy(bool multi);  // workgroups per CU of the score kernel
 hipError_t launch_topk_score(const TopkArgs& a, long long grid, hipStream_t stream);
 hipError_t launch_topk_merge(const unsigned long long* part, long long rows, int k, int nslab, int* ids, float* scores,
                              hipStream_t stream);
+// The same three for k up to kTopkWideMaxK (als_topk_wide.hip); TopkArgs as above, empty slots of `part` are key 0.
+int topk_wide_score_occupancy(bool multi);
+hipError_t launch_topk_wide_score(const TopkArgs& a, long long grid, hipStream_t stream);
+hipError_t launch_topk_wide_merge(const unsigned long long* part, long long rows, int k, int nslab, int* ids, float* scores,
+                                  hipStream_t stream);
 // part: 4 x rows doubles; out: (count, precision, recall, ndcg)
 hipError_t launch_topk_metrics(const int* ids, long long rows, int k, const void* rowptr, int rowptr64, const int* colidx,
                                const float* val, double* part, double* out, hipStream_t stream);

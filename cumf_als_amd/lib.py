@@ -102,6 +102,8 @@ IMPLICIT_ABI = {
 TOPK_ABI = {
     "cumf_topk_available": (_i, [_i, _i]),
     "cumf_topk": (_i, [_fp, _l, _fp, _l, _i, _vp, _i, _ip, _i, _ip, _fp, _vp]),
+    "cumf_topk_wide_available": (_i, [_i, _i]),
+    "cumf_topk_wide": (_i, [_fp, _l, _fp, _l, _i, _vp, _i, _ip, _i, _ip, _fp, _vp]),
     "cumf_ranking_metrics": (_i, [_ip, _l, _i, _vp, _i, _ip, _fp, _vp, _vp]),
 }
 # include/cumf_nnls_capi.h (non-negative ALS, als_nnls.cpp)

@@ -21,8 +21,9 @@
  *
  * Conventions of cumf_als_capi.h: DEVICE pointers of the calling process, `stream` a hipStream_t passed as void* (NULL = the
  * default stream), 0 on success or a HIP error code after printing the reason to stderr, no CPU fallback.  Row pointers are
- * int32 or int64 (rowptr_is_64), as in cumf_plan_create.  Scope: 1 <= f <= 512, 1 <= k <= 128, 0 <= ncand < 2^31, one GPU;
- * anything else is refused.  Every result is bit-identical from run to run (no float atomics).
+ * int32 or int64 (rowptr_is_64), as in cumf_plan_create.  Scope: 1 <= f <= 512, 1 <= k <= 128 (cumf_topk) or 1 <= k <= 2048
+ * (cumf_topk_wide), 0 <= ncand < 2^31, one GPU; anything else is refused.  Every result is bit-identical from run to run (no
+ * float atomics).
  */
 #ifndef CUMF_TOPK_CAPI_H_
 #define CUMF_TOPK_CAPI_H_
@@ -38,6 +39,14 @@ int cumf_topk_available(int f, int k);
  * excl_colidx are both NULL when nothing is excluded. */
 int cumf_topk(const float* Q, long rows, const float* C, long ncand, int f, const void* excl_rowptr, int rowptr_is_64,
               const int* excl_colidx, int k, int* ids, float* scores, void* stream);
+
+/* 1 when cumf_topk_wide takes (f, k): 1 <= f <= 512 and 1 <= k <= 2048.  Host only. */
+int cumf_topk_wide_available(int f, int k);
+
+/* cumf_topk's arguments, contract and result (ids, scores, order, -1 / -inf padding, -0 -> +0), for k up to 2048: the list of
+ * a query lives in device scratch and takes its survivors by a rank merge.  Up to k = 128 it returns what cumf_topk returns. */
+int cumf_topk_wide(const float* Q, long rows, const float* C, long ncand, int f, const void* excl_rowptr, int rowptr_is_64,
+                   const int* excl_colidx, int k, int* ids, float* scores, void* stream);
 
 /* precision@k, recall@k and NDCG@k of `ids` (rows x k) against the held-out CSR; test_val may be NULL. */
 int cumf_ranking_metrics(const int* ids, long rows, int k, const void* test_rowptr, int rowptr_is_64, const int* test_colidx,

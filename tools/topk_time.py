@@ -6,7 +6,9 @@ same job done in torch (chunked fp32 torch.mm, training entries set to -inf, tor
 id sets agree, counted over the queries whose k-th and (k+1)-th torch scores are separated.  One JSON line per
 configuration.  Kernel shares come from a separate run under
 `rocprofv3 --kernel-trace --stats -- python tools/topk_time.py --no-torch`.
-  python tools/topk_time.py [--f 64 100] [--k 10 100] [--side x theta] [--iters 3] [--warmup 1] [--no-torch]"""
+  python tools/topk_time.py [--f 64 100] [--k 10 100] [--side x theta] [--iters 3] [--warmup 1] [--no-torch] [--wide]
+k above 128 goes to cumf_topk_wide; --wide takes every k there and, up to k = 128, times cumf_topk beside it in alternation
+(profiles/topk_wide/topk_time.jsonl: --wide --k 128 256 1000)."""
 import argparse
 import json
 import os
@@ -53,6 +55,34 @@ def timed(fn, iters, warmup):
     return sorted(ms), out
 
 
+def wide_topk(query, cand, k, seen):
+    """cumf_topk_wide called directly, so that k <= 128 reaches it too (als.topk takes those to cumf_topk)."""
+    from cumf_als_amd import lib
+
+    ids = torch.empty((query.shape[0], k), dtype=torch.int32, device=query.device)
+    sc = torch.empty((query.shape[0], k), dtype=torch.float32, device=query.device)
+    lib.check(lib.load().cumf_topk_wide(query.data_ptr(), query.shape[0], cand.data_ptr(), cand.shape[0], query.shape[1],
+                                        seen[0].data_ptr(), int(seen[0].dtype == torch.int64), seen[1].data_ptr(), k,
+                                        ids.data_ptr(), sc.data_ptr(), None), "cumf_topk_wide")
+    return ids, sc
+
+
+def timed_alternating(fns, iters, warmup):
+    """`timed` for several callables, one call of each in turn: sorted ms per callable, and the last result of the last."""
+    ms = [[] for _ in fns]
+    out = None
+    for it in range(warmup + iters):
+        for i, fn in enumerate(fns):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            out = fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                ms[i].append(ev[0].elapsed_time(ev[1]))
+    return [sorted(m) for m in ms], out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="netflix")
@@ -62,6 +92,8 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-torch", action="store_true", help="time cumf_topk only (the profiling run)")
+    ap.add_argument("--wide", action="store_true",
+                    help="every k through cumf_topk_wide (k up to 2048); up to k = 128 cumf_topk beside it, alternated")
     a = ap.parse_args()
     shp = datagen.SHAPES[a.shape]
     r = datagen.synth_ratings(shp["m"], shp["n"], shp["nnz"], shp["nnz_test"], seed=0, device="cuda")
@@ -76,10 +108,20 @@ def main() -> int:
             rows, ncand = query.shape[0], cand.shape[0]
             floor_ms = 2.0 * rows * ncand * f / PEAK_FP32_MFMA * 1e3
             for k in a.k:
-                ms, (ids, sc) = timed(lambda: als.topk(query, cand, k, seen), a.iters, a.warmup)
+                narrow = None
+                if a.wide:  # cumf_topk_wide, beside cumf_topk in alternation where both take k
+                    fns = [lambda: als.topk(query, cand, k, seen)] if als.topk_available(f, k) else []
+                    *narrow, ms = timed_alternating(fns + [lambda: wide_topk(query, cand, k, seen)], a.iters, a.warmup)[0]
+                    ids, sc = wide_topk(query, cand, k, seen)
+                else:
+                    ms, (ids, sc) = timed(lambda: als.topk(query, cand, k, seen), a.iters, a.warmup)
                 out = {"shape": a.shape, "f": f, "k": k, "side": side, "rows": rows, "ncand": ncand,
+                       "entry": "cumf_topk_wide" if a.wide or k > 128 else "cumf_topk",
                        "topk_ms_median": round(ms[len(ms) // 2], 3), "topk_ms": [round(v, 3) for v in ms],
                        "fp32_mfma_floor_ms": round(floor_ms, 3), "floor_fraction": round(floor_ms / ms[len(ms) // 2], 3)}
+                if narrow:
+                    out.update({"cumf_topk_ms_median": round(narrow[0][len(narrow[0]) // 2], 3),
+                                "cumf_topk_ms": [round(v, 3) for v in narrow[0]]})
                 if not a.no_torch:
                     tms, (tids, tsc) = timed(lambda: torch_topk(query, cand, k, *seen), a.iters, a.warmup)
                     sep = (tsc[:, k - 1] - tsc[:, k]) > 1e-5 * tsc[:, k - 1].abs().clamp(min=1.0)
